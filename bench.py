@@ -11,7 +11,10 @@ scaling: S scenes per rank); there is no collective inside the render.
 
 `python bench.py --gpus N` without a torchrun environment spawns its own N ranks (torch.distributed.run, 127.0.0.1).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets up, warms up (--warmup), times --steps steps, writes the last step's outputs (--dump-outputs DIR) and prints ONE JSON
+line on rank 0: metric, value (rays/s), unit, higher_is_better, dtype, ms_per_step, config.  `--full` runs everything else as well and adds
+to the line (at N > 1 too: sampling and the shortened recons leg on every rank):
+  samples_per_s, mean_samples_per_ray, rays_at_step_cap, hit_rays_per_step_per_gpu : from one untimed stat pass with sample counts.
   roofline      : the shading kernel's ALGORITHMIC bytes (288 B/sample + per-hitting-ray bytes) / its mean launch
                   time measured with HIP events on the launch stream, against the 8 TB/s HBM peak.
   cpu_baseline  : the CPU oracle (reference-shaped loop over the C restatement + PyTorch-CPU decode) timed on the
@@ -45,6 +48,7 @@ HBM_PEAK_GBS = 8000.0          # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8
 MFMA_PEAK_TFLOPS = 2500.0      # same guide: dense bf16 MFMA peak (no sparsity)
 BYTES_PER_SAMPLE = 288         # 3 planes x 4 corners x 6 channels x 4 B
 UNET_FLOP_PER_SCENE = 2.18e11  # cars UNet forward
+DUMP_RAYS = 1 << 20            # --dump-outputs: rays written (3 + 1 + 3 float32 + 1 float64 per ray: 36 MB)
 
 
 def parse_args():
@@ -75,6 +79,13 @@ def parse_args():
     ap.add_argument("--ddim-steps", type=int, default=50)
     ap.add_argument("--no-full-recons", action="store_true", help="skip the two whole reconstruction batches (configs[2] as shipped: ~4 s; configs[4]'s "
                     "Langevin x guidance schedule under bf16 + fp16 planes: ~20 s)")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beside the headline as well: the stat pass (sample counts, boundary "
+                    "tests), the roofline and the stages alone, cpu_baseline, gpu_baseline, the uniform / dir variants, ddim, sampling, recons.  Without it "
+                    "the run sets up, warms up, times --steps steps, writes --dump-outputs and prints the headline line; --no-extras / --no-cpu-baseline / "
+                    "--cpu-views / --b1-views / --ddim-steps / --no-full-recons act under --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / float64): "
+                    "image (R,3), depth (R,), image_u8 (R,3, the uint8 views as float32) over R rays, and ray_index (R,) -- the flat ray indices into "
+                    "(scenes, views, size, size) of rank 0; all rays up to 2^20 of them, else a fixed seeded sample of 2^20 (36 MB)")
     return ap.parse_args()
 
 
@@ -248,15 +259,17 @@ def main():
             elapsed = float(t.item())
         return elapsed, events, out
 
-    stats = stat_pass(planes, bits)
-    log(f"stat pass done: {stats['n_samples']} samples, overflow {stats['overflow']}, boundary tests {stats['boundary']}")
+    stats = None
+    if args.full:
+        stats = stat_pass(planes, bits)
+        log(f"stat pass done: {stats['n_samples']} samples, overflow {stats['overflow']}, boundary tests {stats['boundary']}")
     code_dev = code_cpu.to(dev)                              # (only read if a batch must be redone through the stepwise path)
     # (r06) with next_batch, stage A of step i+1 runs on a second stream beside the shading kernel of step i: the events of the timed region then bracket the shading
     # kernel WITH that company (what `roofline` must report: the kernel's launches of the timed region) and no longer stage A.  A short untimed loop without the
     # prefetch, AHEAD of the timed region (whose launches stay the last ones of the process: tools/prof_render.sh), gives both stages alone, on this box, in this process
     alone = None
     prefetching = not (args.no_prefetch or args.packed_loop or rays is not None)
-    if prefetching:
+    if prefetching and args.full:
         args.no_prefetch = True
         _, ev_alone, _ = timed(planes, bits, 5, 10, code_dev)
         args.no_prefetch = False
@@ -264,49 +277,13 @@ def main():
         log(f"stages alone (no prefetch): first_hit {alone['first_hit_ms']:.3f} ms, shade {alone['shade_ms']:.3f} ms")
     elapsed, kernel_events, out = timed(planes, bits, args.warmup, args.steps, code_dev)
     per_rank = pending.get("per_rank")
-    n_samples = stats["n_samples"]
-    if multi:
-        tot = torch.tensor([n_samples], dtype=torch.float64, device=dev)
-        dist.all_reduce(tot)
-        n_samples_all = int(tot.item())
-    else:
-        n_samples_all = n_samples
     ms_per_step = elapsed / args.steps * 1e3
     log(f"timed region done: {ms_per_step:.2f} ms/step")
     rays_per_s = world * n_rays / (elapsed / args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, ns, nv, hw)
+        log(f"outputs of the last timed step written to {args.dump_outputs}")
 
-    first_hit_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in kernel_events])) if alone is None else alone["first_hit_ms"]
-    shade_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in kernel_events]))
-    # dominant kernel = k_shade_mfma (gather + MLP + composite).  Its algorithmic bytes: 288 B per sample it shades plus,
-    # per hitting ray, 8 B queue entry + 20 B outputs (+ 24 B ray when ray arrays are read).
-    n_hit = stats["n_hit"]
-    bytes_per_sample = BYTES_PER_SAMPLE if args.plane_dtype == "float32" else BYTES_PER_SAMPLE // 2     # 288 B per sample in fp32, 144 B with fp16 planes
-    algo_bytes = n_samples * bytes_per_sample + n_hit * bytes_per_hit_ray
-    achieved = algo_bytes / (shade_ms * 1e-3) / 1e9
-    first_hit_bytes = n_rays * (24 if args.ray_arrays else 0) + (n_rays - n_hit) * 20 + n_hit * 8
-
-    # HBM bytes per launch from the PMC counters: they cannot be read from inside the process that is being timed (rocprofv3 wraps the
-    # whole command and a counter pass serialises every launch), so `traffic` is the figure of the most recent tools/prof_render.sh session
-    # on THIS workload and kernel form; `traffic_source` says which session (file, the commit it profiled, the rocprofv3 launch average of the
-    # same session) so that the number can be traced to profiles/
-    traffic, traffic_source = None, None
-    try:
-        tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
-        w = tj["workload"]
-        if (w["scenes"], w["views"], w["size"], w["variant"], w["plane_dtype"]) == (ns, nv, hw, args.variant, args.plane_dtype) and tj["kernel"].startswith("k_shade_mfma") \
-                and w.get("ray_source", "arrays") == ("arrays" if args.ray_arrays else "cameras") \
-                and int(tj.get("dir_products", 3)) == int(dec.shade_dir_products):
-            traffic_source = {k: tj.get(k) for k in ("source", "profiled_commit", "kernel", "rocprof_launch_ms_avg_timed_steps", "rocprof_launches_averaged",
-                                                     "hip_event_launch_ms_same_run", "method", "render_build_id")}
-            from ssdnerf_amd.build import render_build_id
-            mine = render_build_id()
-            if tj.get("render_build_id") == mine:                    # (r06) the session profiled a library built from THESE render sources with THESE settings
-                traffic = tj["hbm_bytes_per_launch"]
-            else:
-                traffic_source["refused"] = (f"the profiling session's library ({tj.get('render_build_id')}) is not the one timed here ({mine}): "
-                                             "traffic is null until tools/prof_render.sh has been run on this build")
-    except Exception:
-        pass
     result = {
         "metric": "rays/s (rendered-views/s = rays/s / 16384), SRN Cars 128x128 novel-view render of cached triplanes",
         "value": rays_per_s, "unit": "rays/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -326,37 +303,84 @@ def main():
                                   "launches -- a raised flag redoes that batch into its own output tensors; --sync-overflow-check restores the r04 read before the next launch)") +
                                  ("" if args.no_prefetch or args.packed_loop else "; next_batch: stage A of the next step is launched on a second stream beside this step's shading kernel (r06; --no-prefetch: the r05 step)"),
                    "collective": "all_gather(uint8 views), overlapped with the next step's render" if multi else "none"},
-        "views_per_s": rays_per_s / (hw * hw), "samples_per_s": n_samples_all / (elapsed / args.steps),
-        "mean_samples_per_ray": n_samples / n_rays, "rays_at_step_cap": stats["overflow"],
-        "roofline": {"bound": "hbm", "kernel": "k_shade_mfma", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes_per_launch": algo_bytes,
-                     "launch_ms": shade_ms, "launches_per_step": 1,
-                     "launch_ms_alone": None if alone is None else alone["shade_ms"],
-                     "frac_alone": None if alone is None else algo_bytes / (alone["shade_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                     "company": None if alone is None else "the timed region's launches share the chip with stage A of the NEXT step (second stream, nerf.render's next_batch): launch_ms / "
-                                                           "frac are measured with that company; launch_ms_alone / frac_alone in a short loop without it (--no-prefetch times that loop)",
-                     "note": f"algorithmic = {bytes_per_sample} B/sample + {bytes_per_hit_ray} B per hitting ray; planes (1.5 MiB/scene) are L2-resident, so real HBM "
-                             "traffic is far below this (PMC numbers in DESIGN.md / profiles/)",
-                     "other_kernels": {"first_hit (k_ray_cull + k_survivor_march)": {
-                         "launch_ms": first_hit_ms, "hidden_beside_the_previous_steps_shading_kernel": prefetching, "algorithmic_bytes_per_launch": first_hit_bytes,
-                         "achieved_GBs": first_hit_bytes / (first_hit_ms * 1e-3) / 1e9}}},
-        "hit_rays_per_step_per_gpu": n_hit,
+        "views_per_s": rays_per_s / (hw * hw),
         "per_rank": None if per_rank is None else {
             "ranks": per_rank, "slowest_rank": max(per_rank, key=lambda r: r["ms_per_step"])["rank"],
             "note": "ms_per_step: the rank's own wall clock over the timed steps (the line's ms_per_step is the max); render_ms: HIP events around its two "
                     "render launches; gather_wait_ms: HIP events around every wait of its compute stream for an all-gather (0 when the collective hides "
                     "behind the next render)"},
-        "boundary_rays": {"termination_tests_within_2e-6_of_T_thresh": stats["boundary"], "samples_per_step_per_gpu": n_samples},
     }
+    if args.dry_nccl:
+        result["dry_nccl"] = {"backend": dist.get_backend(), "world_size": world,
+                              "note": "N > 1 code path on ONE rank over RCCL: a self-check of initialisation, stream ordering and graph capture beside the "
+                                      "collective library's threads -- not a scaling measurement"}
+    if args.full:
+        n_samples = stats["n_samples"]
+        if multi:
+            tot = torch.tensor([n_samples], dtype=torch.float64, device=dev)
+            dist.all_reduce(tot)
+            n_samples_all = int(tot.item())
+        else:
+            n_samples_all = n_samples
 
-    extras = rank == 0 and not multi and not args.no_extras
+        first_hit_ms = float(np.mean([e[0].elapsed_time(e[1]) for e in kernel_events])) if alone is None else alone["first_hit_ms"]
+        shade_ms = float(np.mean([e[1].elapsed_time(e[2]) for e in kernel_events]))
+        # dominant kernel = k_shade_mfma (gather + MLP + composite).  Its algorithmic bytes: 288 B per sample it shades plus,
+        # per hitting ray, 8 B queue entry + 20 B outputs (+ 24 B ray when ray arrays are read).
+        n_hit = stats["n_hit"]
+        bytes_per_sample = BYTES_PER_SAMPLE if args.plane_dtype == "float32" else BYTES_PER_SAMPLE // 2     # 288 B per sample in fp32, 144 B with fp16 planes
+        algo_bytes = n_samples * bytes_per_sample + n_hit * bytes_per_hit_ray
+        achieved = algo_bytes / (shade_ms * 1e-3) / 1e9
+        first_hit_bytes = n_rays * (24 if args.ray_arrays else 0) + (n_rays - n_hit) * 20 + n_hit * 8
+
+        # HBM bytes per launch from the PMC counters: they cannot be read from inside the process that is being timed (rocprofv3 wraps the
+        # whole command and a counter pass serialises every launch), so `traffic` is the figure of the most recent tools/prof_render.sh session
+        # on THIS workload and kernel form; `traffic_source` says which session (file, the commit it profiled, the rocprofv3 launch average of the
+        # same session) so that the number can be traced to profiles/
+        traffic, traffic_source = None, None
+        try:
+            tj = json.load(open(os.path.join(ROOT, "profiles", "traffic_latest.json")))
+            w = tj["workload"]
+            if (w["scenes"], w["views"], w["size"], w["variant"], w["plane_dtype"]) == (ns, nv, hw, args.variant, args.plane_dtype) and tj["kernel"].startswith("k_shade_mfma") \
+                    and w.get("ray_source", "arrays") == ("arrays" if args.ray_arrays else "cameras") \
+                    and int(tj.get("dir_products", 3)) == int(dec.shade_dir_products):
+                traffic_source = {k: tj.get(k) for k in ("source", "profiled_commit", "kernel", "rocprof_launch_ms_avg_timed_steps", "rocprof_launches_averaged",
+                                                         "hip_event_launch_ms_same_run", "method", "render_build_id")}
+                from ssdnerf_amd.build import render_build_id
+                mine = render_build_id()
+                if tj.get("render_build_id") == mine:                    # (r06) the session profiled a library built from THESE render sources with THESE settings
+                    traffic = tj["hbm_bytes_per_launch"]
+                else:
+                    traffic_source["refused"] = (f"the profiling session's library ({tj.get('render_build_id')}) is not the one timed here ({mine}): "
+                                                 "traffic is null until tools/prof_render.sh has been run on this build")
+        except Exception:
+            pass
+        result.update({
+            "samples_per_s": n_samples_all / (elapsed / args.steps), "mean_samples_per_ray": n_samples / n_rays, "rays_at_step_cap": stats["overflow"],
+            "roofline": {"bound": "hbm", "kernel": "k_shade_mfma", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source, "algorithmic_bytes_per_launch": algo_bytes,
+                         "launch_ms": shade_ms, "launches_per_step": 1,
+                         "launch_ms_alone": None if alone is None else alone["shade_ms"],
+                         "frac_alone": None if alone is None else algo_bytes / (alone["shade_ms"] * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                         "company": None if alone is None else "the timed region's launches share the chip with stage A of the NEXT step (second stream, nerf.render's next_batch): launch_ms / "
+                                                               "frac are measured with that company; launch_ms_alone / frac_alone in a short loop without it (--no-prefetch times that loop)",
+                         "note": f"algorithmic = {bytes_per_sample} B/sample + {bytes_per_hit_ray} B per hitting ray; planes (1.5 MiB/scene) are L2-resident, so real HBM "
+                                 "traffic is far below this (PMC numbers in DESIGN.md / profiles/)",
+                         "other_kernels": {"first_hit (k_ray_cull + k_survivor_march)": {
+                             "launch_ms": first_hit_ms, "hidden_beside_the_previous_steps_shading_kernel": prefetching, "algorithmic_bytes_per_launch": first_hit_bytes,
+                             "achieved_GBs": first_hit_bytes / (first_hit_ms * 1e-3) / 1e9}}},
+            "hit_rays_per_step_per_gpu": n_hit,
+            "boundary_rays": {"termination_tests_within_2e-6_of_T_thresh": stats["boundary"], "samples_per_step_per_gpu": n_samples},
+        })
+
+    extras = args.full and rank == 0 and not multi and not args.no_extras
     if extras:
         try:
             result["gpu_baseline"] = gpu_baseline_b1(dec, code_cpu[0].to(dev), bits[0], min(args.b1_views, nv), hw, out, nv, rays_per_s)
             log(f"gpu_baseline done: {result['gpu_baseline']['value']:.3g} rays/s")
         except Exception as e:                               # an extra must never cost the headline line
             result["gpu_baseline"] = {"error": repr(e)}
-    if rank == 0 and not multi and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not multi and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(params, code_cpu[0], bits[0].cpu().numpy(), min(args.cpu_views, nv), hw, out, nv)
         log("cpu_baseline done")
     del out
@@ -395,7 +419,7 @@ def main():
     del planes, code_dev
     torch.cuda.empty_cache()
     model = None
-    if not args.no_extras:                                   # the sampling legs build the config's whole model (every rank at N > 1)
+    if args.full and not args.no_extras:                     # the sampling legs build the config's whole model (every rank at N > 1)
         try:
             model = build_model(dev, rank)
         except Exception as e:
@@ -468,14 +492,29 @@ def main():
             result["recons"] = rec
         except Exception as e:
             result["recons"] = {"error": repr(e)}
-        if args.dry_nccl:
-            result["dry_nccl"] = {"backend": dist.get_backend(), "world_size": world,
-                                  "note": "N > 1 code path on ONE rank over RCCL: a self-check of initialisation, stream ordering and graph capture beside the "
-                                          "collective library's threads -- not a scaling measurement"}
     if rank == 0:
         print(json.dumps(result))
     if multi:
         dist.destroy_process_group()
+
+
+def dump_outputs(path, out, ns, nv, hw):
+    """--dump-outputs: what the last timed step returned to its caller -- the float image, the depth and the uint8 views -- at the same rays in every
+    run with the same arguments (all of them up to DUMP_RAYS, else a sample drawn with a fixed seed), as float32, and the rays' flat indices into
+    (scenes, views, hw, hw) as float64 (exact integers)."""
+    import numpy as np
+    import torch
+    from ssdnerf_amd import nerf
+    n = ns * nv * hw * hw
+    image = out["image"].reshape(n, 3)
+    image_u8 = (out["image_u8"] if "image_u8" in out else nerf.quantize_u8(out["image"])).reshape(n, 3)
+    depth = out["depth"].reshape(n)
+    idx = np.arange(n) if n <= DUMP_RAYS else np.sort(np.random.default_rng(0).choice(n, DUMP_RAYS, replace=False))
+    sel = torch.from_numpy(idx).to(image.device)
+    os.makedirs(path, exist_ok=True)
+    for name, t in (("image", image), ("depth", depth), ("image_u8", image_u8)):
+        np.save(os.path.join(path, f"{name}.npy"), t.index_select(0, sel).float().cpu().numpy())
+    np.save(os.path.join(path, "ray_index.npy"), idx.astype(np.float64))
 
 
 def gpu_baseline_b1(dec, code0, bits0, n_views, hw, gpu_out, nv, fused_rays_per_s):

@@ -36,11 +36,13 @@ def orc():
 @pytest.fixture(scope="session")
 def ref():
     """The reference's own kernels compiled for the CPU (oracle/_ref). Built on demand when
-    /root/reference is present; tests that need it skip when it is absent AND was never built."""
+    the reference sources are present; where they are absent and oracle/_ref was never built, their recorded
+    answers to the tests' calls (tests/_ref_replay.py, tests/golden/ref_calls_<i>.npz)."""
     import oracle
     if oracle.ref_ops("fma") is None and os.path.isdir("/root/reference"):
         oracle.build_ref()
     r = oracle.ref_ops("fma")
     if r is None:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
+        from _ref_replay import Replay
+        return Replay(oracle.ops())
     return r

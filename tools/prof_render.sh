@@ -15,7 +15,7 @@ TAG=${1:-a}; shift
 OUT=$R/gpurun_out/prof_$TAG
 rm -rf $OUT && mkdir -p $OUT
 cd $R
-ARGS="${@:---no-extras --no-cpu-baseline}"      # the default (8 scenes x 251 views) workload: traffic is per launch of THAT
+ARGS="--full ${@:---no-extras --no-cpu-baseline}"      # the default (8 scenes x 251 views) workload: traffic is per launch of THAT; --full: the roofline object
 python bench.py --warmup 10 --steps 20 $ARGS > $OUT/${TAG}_bench_unprofiled.json 2> $OUT/unprofiled_err.log
 rm -rf /tmp/rp_kt
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/rp_kt -o kt -- python bench.py --warmup 10 --steps 20 $ARGS > $OUT/${TAG}_bench_under_rocprof.json 2> $OUT/kt_err.log

@@ -8,4 +8,4 @@ soak positive_control_same_source_compilers_packed_instructions_kept 30000 SSDNE
 } > $O/soak.txt 2>&1
 cat $O/soak.txt | cut -c1-300
 SSDNERF_PROFILED_COMMIT=1fe0acb SSDNERF_PROFILE_ROUND=r06 bash tools/prof_render.sh z > $O/prof.log 2>&1; tail -5 $O/prof.log | cut -c1-300
-python bench.py > $O/bench_full.json 2> $O/bench_full.err; tail -c 600 $O/bench_full.json
+python bench.py --full > $O/bench_full.json 2> $O/bench_full.err; tail -c 600 $O/bench_full.json
