@@ -53,60 +53,7 @@ struct ConvArgs {
     uint32_t ksize, stride, pad, upsample;
     uint32_t G;                  // GroupNorm groups of the output (for gn_sums)
     uint32_t m_tiles, n_tiles;
-    uint32_t* tickets;           // r05, split-K fold: one arrival counter per output tile (all zero on entry, left all zero), or null: the finishing pass is a kernel of its own
 };
-
-// Split-K fold (r05).  A split layer's blocks add their partial sums to the fp32 scratch; until r04 a second kernel (k_conv_splitk_finish / k_conv_f32_finish: 45 launches
-// per UNet forward, 0.2 - 0.3 ms of a 4.3 / 8.3 ms step) read the sums back, added bias / residual, took the GroupNorm statistics and wrote the output.  With
-// `tickets`, the block that ARRIVES LAST at a tile does that itself: every block fences its atomics and takes a ticket; the holder of the last one reads the tile's sums
-// back into its accumulators with agent-scope loads (the other blocks' atomics were performed at the memory side; a plain load could hit a stale line of this XCD's L2),
-// zeroes scratch and ticket, and runs the kernel's ordinary epilogue.  Same sums (the order of the fp32 atomics was already arbitrary), one launch less per layer.
-// Host side: cv_fold_tickets() -- needs the scratch (not the output) as accumulator, room for the tickets behind it, and, for the epilogue's statistics, tiles inside one sample.
-constexpr size_t CV_TICKET_BYTES = 16384;
-static uint32_t* cv_fold_tickets(const ConvArgs& a, void* splitk_ws, size_t splitk_ws_bytes, uint32_t bm, bool want_stats) {
-    // OFF unless SSDNERF_CONV_FOLD=1 (r05, measured on the cars UNet at 8 scenes: fp32 step 8.13 -> 8.87 ms, bf16 4.24 -> 4.50 ms WITH the fold): the finishing
-    // kernel spreads a layer's epilogue over the whole chip, the fold leaves it to the one block per tile that arrives last -- 64 uncached loads per lane in series
-    // with that tile's tail -- and these layers are latency-bound already.  Kept as an opt-in; results equal the finishing pass's (tests/test_unet_fast_gpu.py run with it).
-    static const bool on = [] { const char* e = getenv("SSDNERF_CONV_FOLD"); return e != nullptr && e[0] != '\0' && e[0] != '0'; }();      // (=0 and empty mean off)
-    if (!on || a.splits <= 1 || splitk_ws == nullptr || (void*)a.splitk_ws != splitk_ws) return nullptr;
-    if (splitk_ws_bytes < (size_t)a.M * a.Cout * 4 + CV_TICKET_BYTES || (size_t)a.m_tiles * a.n_tiles * 4 > CV_TICKET_BYTES) return nullptr;
-    if (want_stats && (a.Ho * a.Wo) % bm != 0) return nullptr;
-    return reinterpret_cast<uint32_t*>(reinterpret_cast<unsigned char*>(splitk_ws) + splitk_ws_bytes - CV_TICKET_BYTES);
-}
-// device side, behind a block's atomics: true for the block that arrived last -- its accumulators then hold the tile's complete sums and scratch / ticket are zero again
-template <int TM, int TN>
-SSD_DEV bool cv_fold_last(const ConvArgs& a, f32x16 (&acc)[TM][TN], float* ws, uint32_t* flag_lds, uint32_t tile, uint32_t m0, uint32_t n0, uint32_t row_off, uint32_t col_off, bool PT) {
-    // this block's atomics are acknowledged before its ticket is taken: `s_waitcnt vmcnt(0)` per wave (a workgroup-scope release), then the barrier.  NOT
-    // __threadfence(): an agent-scope release writes the L2's dirty lines back (buffer_wbl2) -- measured: the UNet step 8.1 -> 11.5 ms with it.  The float atomics
-    // and the ticket are device-scope read-modify-writes resolved at one coherence point; the sums are read back with agent-scope loads that bypass this XCD's L2.
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __syncthreads();
-    if (threadIdx.x == 0) *flag_lds = atomicAdd(a.tickets + tile, 1u);
-    __syncthreads();
-    const bool last = *flag_lds == a.splits - 1;
-    __syncthreads();                                                         // (the flag's word belongs to the epilogue's scratch)
-    if (!last) return false;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    const uint32_t lane = threadIdx.x & 63;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const uint32_t m = m0 + row_off + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-                const uint32_t col = n0 + col_off + j * 32 + (lane & 31);
-                float v = 0.f;
-                if (m < a.M && (!PT || col < a.Cout)) {
-                    float* p = ws + (size_t)m * a.Cout + col;
-                    v = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    *p = 0.f;
-                }
-                acc[i][j][e] = v;
-            }
-    if (threadIdx.x == 0) a.tickets[tile] = 0u;
-    return true;
-}
 
 constexpr int CV_BK = 64;                  // bf16 elements per K-tile = 128 bytes per tile row
 constexpr int CV_ROWB = CV_BK * 2;
@@ -537,8 +484,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_conv_igemm_bf16(const ConvArgs
                     const uint32_t col = n0 + wn * 32 * TN + j * 32 + (lane & 31);
                     if (m < a.M && (!PT || col < a.Cout)) unsafeAtomicAdd(a.splitk_ws + (size_t)m * a.Cout + col, acc[i][j][e]);
                 }
-        if (a.tickets == nullptr) return;
-        if (!cv_fold_last<TM, TN>(a, acc, a.splitk_ws, reinterpret_cast<uint32_t*>(lds + LDS_BYTES - 4), tile, m0, n0, wm * 32 * TM, wn * 32 * TN, PT)) return;
+        return;
     }
 
     if constexpr (PS) cv_epilogue_f32<TM, TN, false>(a, acc, lds, m0, n0);
@@ -881,6 +827,9 @@ __global__ __launch_bounds__(256) void k_conv_igemm_f32x2(const ConvArgs a, cons
 
     const uint32_t KT_all = taps * kc;
     const uint32_t kt_begin = (uint32_t)((uint64_t)split * KT_all / a.splits), KT = (uint32_t)((uint64_t)(split + 1) * KT_all / a.splits) - kt_begin;
+    // (never taken: the plan keeps splits <= K-tiles / 2, so every block has K-tiles.  Without it the compiler carries the PT form's accumulators through the K loop in VGPRs as well
+    // and copies them AGPR -> VGPR -> AGPR on every K-tile: 70 -> 84 VGPRs at 64 x 64, 110 -> 168 at 128 x 128.)
+    if (PT && KT == 0) return;
     uint32_t tap = kt_begin / kc, ci = kt_begin % kc;
     set_tap(tap);
     a_load(ci);
@@ -938,8 +887,7 @@ __global__ __launch_bounds__(256) void k_conv_igemm_f32x2(const ConvArgs a, cons
                     const uint32_t col = n0 + wn * 32 * TN + j * 32 + (lane & 31);
                     if (m < a.M && (!PT || col < a.Cout)) unsafeAtomicAdd(yo + (size_t)m * a.Cout + col, acc[i][j][e]);
                 }
-        if (a.tickets == nullptr) return;
-        if (!cv_fold_last<TM, TN>(a, acc, yo, reinterpret_cast<uint32_t*>(lds + LDS_BYTES - 4), tile, m0, n0, wm * 32 * TM, wn * 32 * TN, PT)) return;
+        return;
     }
 
     cv_epilogue_f32<TM, TN, PT>(a, acc, lds, m0, n0);
@@ -1642,6 +1590,73 @@ int cv_launch(ConvArgs& a, hipStream_t st) {
     return 0;
 }
 
+// CUs of the current device, a multiple of 8 (the XCDs); 256 if the query fails
+uint32_t cv_cu_count() {
+    static const uint32_t n = [] {
+        int dev = 0, n_cu = 0;
+        hipDeviceProp_t prop;
+        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
+        if (n_cu < 8) n_cu = 256;
+        return (uint32_t)(n_cu & ~7);
+    }();
+    return n;
+}
+
+// the two-group 256 x 128 kernel: one block per CU (LDS), persistent over the tiles
+template <bool ROWS, bool F32 = false, bool PS = false>
+void cv_launch_pp(ConvArgs& a, hipStream_t st) {
+    a.m_tiles = (a.M + 255) / 256;
+    a.n_tiles = a.Cout / 128;
+    const uint32_t tiles = a.m_tiles * a.n_tiles, n_cu = cv_cu_count();
+    hipLaunchKernelGGL((k_conv_pp_bf16<ROWS, F32, PS>), dim3(tiles < n_cu ? tiles : n_cu), dim3(512), 0, st, a);
+}
+
+// the finishing pass of a split layer: output = sums in ws + bias + residual (+ GroupNorm statistics), ws back to zero.  f32_out: k_conv_f32_finish
+// (ws null: the sums are in the output itself), else k_conv_splitk_finish.  Grid (row slabs, B): rows per block >= one pass of the rows in flight, ~1024 blocks.
+void cv_launch_finish(const ConvArgs& a, bool f32_out, float* ws, hipStream_t st) {
+    const uint32_t HWo = a.Ho * a.Wo, cpr = a.Cout / 8, rstep = 256 / cpr ? 256 / cpr : 1;
+    uint32_t rows = HWo;
+    while (rows > rstep && rows % 2 == 0 && (uint64_t)a.B * (HWo / rows) < 1024) rows /= 2;
+    const dim3 grid((HWo + rows - 1) / rows, a.B);
+    if (f32_out) hipLaunchKernelGGL(k_conv_f32_finish, grid, dim3(256), 0, st, (float*)a.y, ws, a.bias, (const float*)a.res, HWo, cpr, rows, a.gn_sums, a.G);
+    else hipLaunchKernelGGL(k_conv_splitk_finish, grid, dim3(256), 0, st, ws, a.bias, a.res, a.y, HWo, cpr, rows, a.gn_sums, a.G);
+}
+
+// One layer's arguments: x2 null = one input of Cin channels; output size from kernel size (pad ksize / 2), stride and upsampling; the split-K scratch
+// only if it holds the M x Cout fp32 sums.  One K range; the tile counts are set where the kernel is launched.
+ConvArgs cv_args(const void* x, const void* x2, uint32_t Cin1, const void* w, const float* bias, const void* residual, void* y, uint32_t B, uint32_t H,
+                 uint32_t W, uint32_t Cin, uint32_t Cout, uint32_t ksize, uint32_t stride, uint32_t upsample, void* gn_sums, uint32_t gn_groups,
+                 void* splitk_ws, size_t splitk_ws_bytes) {
+    ConvArgs a;
+    a.x = (const unsigned char*)x; a.x2 = (const unsigned char*)x2; a.Cin1 = x2 ? Cin1 : Cin;
+    a.w = (const unsigned char*)w; a.bias = bias; a.res = (const unsigned char*)residual; a.y = (unsigned char*)y;
+    a.gn_sums = (double*)gn_sums; a.G = gn_groups ? gn_groups : 1;
+    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
+    a.ksize = ksize; a.stride = stride; a.pad = ksize / 2; a.upsample = upsample;
+    const uint32_t Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
+    a.Ho = (Hv + 2 * a.pad - ksize) / stride + 1;
+    a.Wo = (Wv + 2 * a.pad - ksize) / stride + 1;
+    a.M = B * a.Ho * a.Wo;                                                   // (the callers check B * Ho * Wo < 2^31)
+    a.splitk_ws = (splitk_ws && splitk_ws_bytes >= (size_t)a.M * Cout * 4) ? (float*)splitk_ws : nullptr;
+    a.splits = 1;
+    a.m_tiles = a.n_tiles = 0;
+    return a;
+}
+
+// checks the entry points share; fn: the entry point's name for the message
+int cv_check_layer(const char* fn, const void* x2, uint32_t Cin1, uint32_t Cin, uint32_t Cout, uint32_t ksize, uint32_t stride, uint32_t upsample) {
+    SSD_REQUIRE(ssdnerf_conv2d_nhwc_bf16_supported(Cin, Cout, ksize, stride, upsample),
+                "%s: needs Cin %% 8 == 0, Cout %% 8 == 0, ksize 1|3, stride 1|2 (no stride with upsample)", fn);
+    SSD_REQUIRE(!x2 || (Cin1 <= Cin && Cin1 % 8 == 0), "%s: the first input's channel count must be a multiple of 8 and <= Cin", fn);
+    SSD_REQUIRE((uint64_t)Cout * ksize * ksize * Cin * 2 < (1ull << 31), "%s: weight tensor too large", fn);
+    return SSDNERF_OK;
+}
+
+int cv_check_gn(const char* fn, const void* gn_sums, uint32_t gn_groups, uint32_t Cout) {
+    SSD_REQUIRE(!gn_sums || (gn_groups > 0 && Cout % gn_groups == 0 && (Cout / gn_groups) % 4 == 0), "%s: fused GroupNorm statistics need groups of a multiple of 4 channels", fn);
+    return SSDNERF_OK;
+}
+
 }  // namespace
 
 // tile choice: the largest tile that still gives every CU (256) a block; tile_hint 1/2/3/4 forces 128x128 / 64x128 / 64x64 / 256x128
@@ -1705,89 +1720,48 @@ extern "C" int ssdnerf_conv2d_nhwc_f32x2(const void* x, const void* x2, uint32_t
                                          void* stream) {
     if (B == 0 || H == 0 || W == 0) return SSDNERF_OK;
     SSD_REQUIRE(x && w_hi && w_lo && y, "conv2d_nhwc_f32x2: null pointer");
-    SSD_REQUIRE(ssdnerf_conv2d_nhwc_bf16_supported(Cin, Cout, ksize, stride, upsample),
-                "conv2d_nhwc_f32x2: needs Cin %% 8 == 0, Cout %% 8 == 0, ksize 1|3, stride 1|2 (no stride with upsample)");
-    if (!x2) Cin1 = Cin;
-    SSD_REQUIRE(Cin1 <= Cin && Cin1 % 8 == 0 && (x2 || Cin1 == Cin), "conv2d_nhwc_f32x2: the first input's channel count must be a multiple of 8 and <= Cin");
-    SSD_REQUIRE((uint64_t)Cout * ksize * ksize * Cin * 2 < (1ull << 31), "conv2d_nhwc_f32x2: weight tensor too large");
-    SSD_REQUIRE(!gn_sums || (gn_groups > 0 && Cout % gn_groups == 0 && (Cout / gn_groups) % 4 == 0), "conv2d_nhwc_f32x2: fused GroupNorm statistics need groups of a multiple of 4 channels");
-    ConvArgs a;
-    a.tickets = nullptr;
-    a.x2 = (const unsigned char*)x2; a.Cin1 = Cin1;
-    a.x = (const unsigned char*)x; a.w = (const unsigned char*)w_hi; a.bias = bias; a.res = (const unsigned char*)residual; a.y = (unsigned char*)y;
-    a.gn_sums = (double*)gn_sums; a.G = gn_groups ? gn_groups : 1;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.ksize = ksize; a.stride = stride; a.pad = ksize / 2; a.upsample = upsample;
-    const uint32_t Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
-    a.Ho = (Hv + 2 * a.pad - ksize) / stride + 1;
-    a.Wo = (Wv + 2 * a.pad - ksize) / stride + 1;
+    if (const int e = cv_check_layer("conv2d_nhwc_f32x2", x2, Cin1, Cin, Cout, ksize, stride, upsample)) return e;
+    if (const int e = cv_check_gn("conv2d_nhwc_f32x2", gn_sums, gn_groups, Cout)) return e;
+    ConvArgs a = cv_args(x, x2, Cin1, w_hi, bias, residual, y, B, H, W, Cin, Cout, ksize, stride, upsample, gn_sums, gn_groups, splitk_ws, splitk_ws_bytes);
     SSD_REQUIRE((uint64_t)B * a.Ho * a.Wo < (1ull << 31), "conv2d_nhwc_f32x2: tensor too large");
-    a.M = B * a.Ho * a.Wo;
-    a.splitk_ws = (splitk_ws && splitk_ws_bytes >= (size_t)a.M * Cout * 4) ? (float*)splitk_ws : nullptr;
     const int plan = ssdnerf_conv2d_nhwc_f32x2_plan(a.M, Cin, Cout, ksize, tile_hint, splits_hint);
     const int choice = plan & 0xff;
     const uint32_t splits = (uint32_t)plan >> 8, bm = choice == 1 ? 128 : 64;
     if (choice == 1) SSD_REQUIRE(Cout % 128 == 0, "conv2d_nhwc_f32x2: 128-wide tiles need Cout %% 128 == 0");
-    a.splits = splits;
     SSD_REQUIRE(!gn_sums || splits > 1 || (a.Ho * a.Wo) % bm == 0, "conv2d_nhwc_f32x2: fused GroupNorm statistics need Ho*Wo to be a multiple of the M tile");
     hipStream_t st = (hipStream_t)stream;
-    double* stats = a.gn_sums;
-    a.tickets = nullptr;
-    a.m_tiles = (a.M + bm - 1) / bm; a.n_tiles = (Cout + bm - 1) / bm;
-    if (splits > 1) {
-        a.tickets = cv_fold_tickets(a, splitk_ws, splitk_ws_bytes, bm, stats != nullptr);
-        if (!a.tickets) a.gn_sums = nullptr;                                 // (folded: the last block's epilogue takes the statistics)
-        if (!a.splitk_ws && !y_is_zero && hipMemsetAsync(y, 0, (size_t)a.M * Cout * 4, st) != hipSuccess) return ssdnerf_fail(SSDNERF_E_LAUNCH, "conv2d_nhwc_f32x2: memset failed");
-    } else {
-        a.splitk_ws = nullptr;
-    }
     // r03: the two-group 256 x 128 kernel (k_conv_pp_bf16<ROWS, F32 = true>) takes the layers its bf16 form takes (tile_hint 5 / 6 force it);
     // it needs the lo weights directly behind the hi ones (one buffer descriptor serves both terms)
-    static const bool pp_auto = getenv("SSDNERF_CONV_NO_TWO_GROUP") == nullptr;
-    const bool pp_ok = Cin % 32 == 0 && Cin1 % 32 == 0 && Cout % 128 == 0 && (const unsigned char*)w_lo == (const unsigned char*)w_hi + (size_t)Cout * ksize * ksize * Cin * 2
+    const bool pp_ok = Cin % 32 == 0 && a.Cin1 % 32 == 0 && Cout % 128 == 0 && (const unsigned char*)w_lo == (const unsigned char*)w_hi + (size_t)Cout * ksize * ksize * Cin * 2
                        && (uint64_t)B * H * W * Cin * 4 < (1ull << 31) && (!gn_sums || (a.Ho * a.Wo) % 256 == 0);
     // (measured, profiles/r03/m_two_group_fp32.txt: the row-reuse form equals k_conv3x3_f32x2_rows on the 128 x 128 level -- 164 vs 166 us per layer --;
     // the generic form is SLOWER than k_conv_igemm_f32x2<2, 2> on the upsampling layer, 510 vs 447 us, so only the former is picked automatically)
-    if (tile_hint == 0 && pp_auto && pp_ok && splits == 1 && ksize == 3 && stride == 1 && a.M >= 32768 && !upsample && (W == 128 || W == 64) && (H * W) % 256 == 0)
+    if (tile_hint == 0 && pp_ok && splits == 1 && ksize == 3 && stride == 1 && a.M >= 32768 && !upsample && (W == 128 || W == 64) && (H * W) % 256 == 0)
         tile_hint = 6;
     if (tile_hint == 5 || tile_hint == 6) {
         SSD_REQUIRE(pp_ok, "conv2d_nhwc_f32x2: the 256 x 128 kernel needs Cin %% 32 == 0, Cout %% 128 == 0 and w_lo directly behind w_hi");
-        a.splits = 1; a.splitk_ws = nullptr; a.gn_sums = stats;
-        a.m_tiles = (a.M + 255) / 256; a.n_tiles = Cout / 128;
         const bool pp_rows = tile_hint == 6 && ksize == 3 && stride == 1 && !upsample && (W == 128 || W == 64 || W == 32) && (H * W) % 256 == 0;
-        static int n_cu = 0;
-        if (n_cu == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-            if (n_cu < 8) n_cu = 256;
-            n_cu &= ~7;
-        }
-        const uint32_t tiles = a.m_tiles * a.n_tiles, grid = tiles < (uint32_t)n_cu ? tiles : (uint32_t)n_cu;
-        if (pp_rows) hipLaunchKernelGGL((k_conv_pp_bf16<true, true>), dim3(grid), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_conv_pp_bf16<false, true>), dim3(grid), dim3(512), 0, st, a);
+        if (pp_rows) cv_launch_pp<true, true>(a, st); else cv_launch_pp<false, true>(a, st);
         SSD_CHECK_LAUNCH("conv2d_nhwc_f32x2");
         return SSDNERF_OK;
     }
+    // split-K: the partial sums go to the scratch or, without one, to the output, which must then be zero
+    a.splits = splits;
+    if (splits > 1 && !a.splitk_ws && !y_is_zero && hipMemsetAsync(y, 0, (size_t)a.M * Cout * 4, st) != hipSuccess)
+        return ssdnerf_fail(SSDNERF_E_LAUNCH, "conv2d_nhwc_f32x2: memset failed");
     a.m_tiles = (a.M + bm - 1) / bm; a.n_tiles = (Cout + bm - 1) / bm;
     // 3x3 / stride 1 layers whose 128-pixel tiles are whole image rows take the row-reuse kernel (A loaded once per kh, shared by the three kw taps)
-    static const bool rows_ok = getenv("SSDNERF_CONV_NO_ROW_REUSE") == nullptr;
-    const bool rows = rows_ok && Cin % 64 == 0 && Cin1 % 64 == 0 && choice == 1 && splits == 1 && ksize == 3 && stride == 1 && !upsample && (W == 128 || W == 64 || W == 32) && (H * W) % 128 == 0;
+    const bool rows = Cin % 64 == 0 && a.Cin1 % 64 == 0 && choice == 1 && splits == 1 && ksize == 3 && stride == 1 && !upsample && (W == 128 || W == 64 || W == 32) && (H * W) % 128 == 0;
     if (rows) hipLaunchKernelGGL(k_conv3x3_f32x2_rows, dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a, (const unsigned char*)w_lo);
     else {
-        const bool partial = Cin1 % 32 != 0 || (Cin - Cin1) % 32 != 0 || Cout % bm != 0;
+        const bool partial = a.Cin1 % 32 != 0 || (Cin - a.Cin1) % 32 != 0 || Cout % bm != 0;
         const dim3 grid(a.m_tiles * a.n_tiles * splits);
         if (choice == 1 && partial) hipLaunchKernelGGL((k_conv_igemm_f32x2<2, 2, true>), grid, dim3(256), 0, st, a, (const unsigned char*)w_lo);
         else if (choice == 1) hipLaunchKernelGGL((k_conv_igemm_f32x2<2, 2, false>), grid, dim3(256), 0, st, a, (const unsigned char*)w_lo);
         else if (partial) hipLaunchKernelGGL((k_conv_igemm_f32x2<1, 1, true>), grid, dim3(256), 0, st, a, (const unsigned char*)w_lo);
         else hipLaunchKernelGGL((k_conv_igemm_f32x2<1, 1, false>), grid, dim3(256), 0, st, a, (const unsigned char*)w_lo);
     }
-    if (splits > 1 && !a.tickets) {
-        const uint32_t HWo = a.Ho * a.Wo, cpr = Cout / 8, rstep = 256 / cpr ? 256 / cpr : 1;
-        uint32_t rows = HWo;
-        while (rows > rstep && rows % 2 == 0 && (uint64_t)B * (HWo / rows) < 1024) rows /= 2;
-        hipLaunchKernelGGL(k_conv_f32_finish, dim3((HWo + rows - 1) / rows, B), dim3(256), 0, st, (float*)y, a.splitk_ws, bias, (const float*)residual, HWo, cpr, rows, stats, a.G);
-    }
+    if (splits > 1) cv_launch_finish(a, true, a.splitk_ws, st);
     SSD_CHECK_LAUNCH("conv2d_nhwc_f32x2");
     return SSDNERF_OK;
 }
@@ -1819,13 +1793,11 @@ static int cv_ps_plan(uint32_t M, uint32_t Cin, uint32_t Cout, uint32_t ksize, i
 //      (tile and split-K from ssdnerf_conv2d_nhwc_f32x2_plan): same fp32-class products as k_conv_igemm_f32x2, summed in another order.
 // _supported returns which (0 = neither), so that the host asks its GroupNorm for the split output exactly then.
 extern "C" int ssdnerf_conv2d_nhwc_f32x2_presplit_supported(uint32_t B, uint32_t H, uint32_t W, uint32_t Cin, uint32_t Cout, uint32_t ksize, int with_gn_sums) {
-    static const bool pp_auto = getenv("SSDNERF_CONV_NO_TWO_GROUP") == nullptr && getenv("SSDNERF_CONV_NO_PRESPLIT") == nullptr;
-    static const bool small_auto = getenv("SSDNERF_CONV_NO_PRESPLIT") == nullptr && getenv("SSDNERF_CONV_NO_PRESPLIT_SMALL") == nullptr;
     const uint64_t M = (uint64_t)B * H * W;
     if (B == 0 || H == 0 || W == 0 || (ksize != 1 && ksize != 3) || Cin % 32 != 0 || M >= (1ull << 31) || M * Cin * 4 >= (1ull << 31)
         || (uint64_t)Cout * ksize * ksize * Cin * 4 >= (1ull << 31)) return 0;
-    if (pp_auto && ksize == 3 && Cout % 128 == 0 && (W == 128 || W == 64) && (H * W) % 256 == 0 && M >= 32768) return 1;
-    if (!small_auto || Cout % 64 != 0 || M * Cout * 4 >= (1ull << 31)) return 0;
+    if (ksize == 3 && Cout % 128 == 0 && (W == 128 || W == 64) && (H * W) % 256 == 0 && M >= 32768) return 1;
+    if (Cout % 64 != 0 || M * Cout * 4 >= (1ull << 31)) return 0;
     const int plan = cv_ps_plan((uint32_t)M, Cin, Cout, ksize, 0, 0);
     const uint32_t bm = (plan & 0xff) == 1 ? 128 : 64, splits = (uint32_t)plan >> 8;
     if (with_gn_sums && splits == 1 && (H * W) % bm != 0) return 0;
@@ -1842,56 +1814,30 @@ extern "C" int ssdnerf_conv2d_nhwc_f32x2_presplit(const void* x_split, const voi
         kind = 2;                                                            // (sweeps: force the generic kernel's PS form with this tile)
     SSD_REQUIRE(kind != 0, "conv2d_nhwc_f32x2_presplit: layer not taken by a pre-split kernel (ask ssdnerf_conv2d_nhwc_f32x2_presplit_supported first)");
     SSD_REQUIRE((const unsigned char*)w_lo == (const unsigned char*)w_hi + (size_t)Cout * ksize * ksize * Cin * 2, "conv2d_nhwc_f32x2_presplit: w_lo must lie directly behind w_hi");
-    SSD_REQUIRE(!gn_sums || (gn_groups > 0 && Cout % gn_groups == 0 && (Cout / gn_groups) % 4 == 0), "conv2d_nhwc_f32x2_presplit: fused GroupNorm statistics need groups of a multiple of 4 channels");
+    if (const int e = cv_check_gn("conv2d_nhwc_f32x2_presplit", gn_sums, gn_groups, Cout)) return e;
     hipStream_t st = (hipStream_t)stream;
-    ConvArgs a;
-    a.tickets = nullptr;
-    a.x2 = nullptr; a.Cin1 = Cin;
-    a.x = (const unsigned char*)x_split; a.w = (const unsigned char*)w_hi; a.bias = bias; a.res = (const unsigned char*)residual; a.y = (unsigned char*)y;
-    a.gn_sums = (double*)gn_sums; a.G = gn_groups ? gn_groups : 1;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.ksize = ksize; a.stride = 1; a.pad = ksize / 2; a.upsample = 0;
-    a.Ho = H; a.Wo = W; a.M = B * H * W;
-    a.splits = 1; a.splitk_ws = nullptr; a.tickets = nullptr;
-    if (kind == 2) {
-        const int plan = cv_ps_plan(a.M, Cin, Cout, ksize, tile_hint, splits_hint);
-        const int choice = plan & 0xff;
-        const uint32_t bm = choice == 1 ? 128 : 64, bn = choice == 3 ? 64 : 128;
-        a.splits = (uint32_t)plan >> 8;
-        SSD_REQUIRE(!gn_sums || a.splits > 1 || (H * W) % bm == 0, "conv2d_nhwc_f32x2_presplit: fused GroupNorm statistics need H*W to be a multiple of the M tile");
-        a.m_tiles = (a.M + bm - 1) / bm; a.n_tiles = Cout / bn;
-        float* ws = (splitk_ws && splitk_ws_bytes >= (size_t)a.M * Cout * 4) ? (float*)splitk_ws : nullptr;
-        double* stats = a.gn_sums;
-        if (a.splits > 1) {
-            if (!ws && hipMemsetAsync(y, 0, (size_t)a.M * Cout * 4, st) != hipSuccess) return ssdnerf_fail(SSDNERF_E_LAUNCH, "conv2d_nhwc_f32x2_presplit: memset failed");
-            a.splitk_ws = ws ? ws : (float*)y;
-            a.tickets = cv_fold_tickets(a, splitk_ws, splitk_ws_bytes, bm, stats != nullptr);
-            if (!a.tickets) a.gn_sums = nullptr;
-        }
-        const dim3 grid(a.m_tiles * a.n_tiles * a.splits);
-        if (choice == 1) hipLaunchKernelGGL((k_conv_igemm_bf16<2, 2, 2, 2, 2, false, true>), grid, dim3(256), 0, st, a);
-        else if (choice == 2) hipLaunchKernelGGL((k_conv_igemm_bf16<1, 2, 2, 2, 3, false, true>), grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((k_conv_igemm_bf16<1, 1, 2, 2, CV_NS_SMALL, false, true>), grid, dim3(256), 0, st, a);
-        if (a.splits > 1 && !a.tickets) {
-            const uint32_t HWo = H * W, cpr = Cout / 8, rstep = 256 / cpr ? 256 / cpr : 1;
-            uint32_t rows = HWo;
-            while (rows > rstep && rows % 2 == 0 && (uint64_t)B * (HWo / rows) < 1024) rows /= 2;
-            hipLaunchKernelGGL(k_conv_f32_finish, dim3((HWo + rows - 1) / rows, B), dim3(256), 0, st, (float*)y, ws, bias, (const float*)residual, HWo, cpr, rows, stats, a.G);
-        }
+    ConvArgs a = cv_args(x_split, nullptr, Cin, w_hi, bias, residual, y, B, H, W, Cin, Cout, ksize, 1, 0, gn_sums, gn_groups, splitk_ws, splitk_ws_bytes);
+    if (kind == 1) {
+        cv_launch_pp<true, true, true>(a, st);
         SSD_CHECK_LAUNCH("conv2d_nhwc_f32x2_presplit");
         return SSDNERF_OK;
     }
-    a.m_tiles = (a.M + 255) / 256; a.n_tiles = Cout / 128;
-    static int n_cu = 0;
-    if (n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-        if (n_cu < 8) n_cu = 256;
-        n_cu &= ~7;
+    const int plan = cv_ps_plan(a.M, Cin, Cout, ksize, tile_hint, splits_hint);
+    const int choice = plan & 0xff;
+    const uint32_t bm = choice == 1 ? 128 : 64, bn = choice == 3 ? 64 : 128;
+    a.splits = (uint32_t)plan >> 8;
+    SSD_REQUIRE(!gn_sums || a.splits > 1 || (H * W) % bm == 0, "conv2d_nhwc_f32x2_presplit: fused GroupNorm statistics need H*W to be a multiple of the M tile");
+    a.m_tiles = (a.M + bm - 1) / bm; a.n_tiles = Cout / bn;
+    float* const ws = a.splitk_ws;
+    if (a.splits > 1 && !ws) {                                               // no scratch: the partial sums go to the output, zeroed here
+        if (hipMemsetAsync(y, 0, (size_t)a.M * Cout * 4, st) != hipSuccess) return ssdnerf_fail(SSDNERF_E_LAUNCH, "conv2d_nhwc_f32x2_presplit: memset failed");
+        a.splitk_ws = (float*)y;
     }
-    const uint32_t tiles = a.m_tiles * a.n_tiles, grid = tiles < (uint32_t)n_cu ? tiles : (uint32_t)n_cu;
-    hipLaunchKernelGGL((k_conv_pp_bf16<true, true, true>), dim3(grid), dim3(512), 0, st, a);
+    const dim3 grid(a.m_tiles * a.n_tiles * a.splits);
+    if (choice == 1) hipLaunchKernelGGL((k_conv_igemm_bf16<2, 2, 2, 2, 2, false, true>), grid, dim3(256), 0, st, a);
+    else if (choice == 2) hipLaunchKernelGGL((k_conv_igemm_bf16<1, 2, 2, 2, 3, false, true>), grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL((k_conv_igemm_bf16<1, 1, 2, 2, CV_NS_SMALL, false, true>), grid, dim3(256), 0, st, a);
+    if (a.splits > 1) cv_launch_finish(a, true, ws, st);
     SSD_CHECK_LAUNCH("conv2d_nhwc_f32x2_presplit");
     return SSDNERF_OK;
 }
@@ -1906,83 +1852,39 @@ extern "C" int ssdnerf_conv2d_nhwc_bf16(const void* x, const void* x2, uint32_t 
                                         int tile_hint, void* splitk_ws, size_t splitk_ws_bytes, int splits_hint, void* stream) {
     if (B == 0 || H == 0 || W == 0) return SSDNERF_OK;
     SSD_REQUIRE(x && w && y, "conv2d_nhwc_bf16: null pointer");
-    SSD_REQUIRE(ssdnerf_conv2d_nhwc_bf16_supported(Cin, Cout, ksize, stride, upsample),
-                "conv2d_nhwc_bf16: needs Cin %% 8 == 0, Cout %% 8 == 0, ksize 1|3, stride 1|2 (no stride with upsample)");
-    SSD_REQUIRE(!gn_sums || (gn_groups > 0 && Cout % gn_groups == 0 && (Cout / gn_groups) % 4 == 0),
-                "conv2d_nhwc_bf16: fused GroupNorm statistics need groups of a multiple of 4 channels");
-    if (!x2) Cin1 = Cin;
-    SSD_REQUIRE(Cin1 <= Cin && Cin1 % 8 == 0 && (x2 || Cin1 == Cin), "conv2d_nhwc_bf16: the first input's channel count must be a multiple of 8 and <= Cin");
-    SSD_REQUIRE((uint64_t)Cout * ksize * ksize * Cin * 2 < (1ull << 31), "conv2d_nhwc_bf16: weight tensor too large");
-    const bool c64 = Cin % 64 == 0 && Cin1 % 64 == 0;                         // what the row-reuse and two-group kernels take
-    ConvArgs a;
-    a.tickets = nullptr;
-    a.x2 = (const unsigned char*)x2; a.Cin1 = Cin1;
-    a.x = (const unsigned char*)x; a.w = (const unsigned char*)w; a.bias = bias; a.res = (const unsigned char*)residual; a.y = (unsigned char*)y;
-    a.gn_sums = (double*)gn_sums; a.G = gn_groups ? gn_groups : 1;
-    a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout;
-    a.ksize = ksize; a.stride = stride; a.pad = ksize / 2; a.upsample = upsample;
-    const uint32_t Hv = upsample ? 2 * H : H, Wv = upsample ? 2 * W : W;
-    a.Ho = (Hv + 2 * a.pad - ksize) / stride + 1;
-    a.Wo = (Wv + 2 * a.pad - ksize) / stride + 1;
+    if (const int e = cv_check_layer("conv2d_nhwc_bf16", x2, Cin1, Cin, Cout, ksize, stride, upsample)) return e;
+    if (const int e = cv_check_gn("conv2d_nhwc_bf16", gn_sums, gn_groups, Cout)) return e;
+    ConvArgs a = cv_args(x, x2, Cin1, w, bias, residual, y, B, H, W, Cin, Cout, ksize, stride, upsample, gn_sums, gn_groups, splitk_ws, splitk_ws_bytes);
     SSD_REQUIRE((uint64_t)B * a.Ho * a.Wo < (1ull << 31) && (uint64_t)B * H * W * Cin * 2 < (1ull << 31), "conv2d_nhwc_bf16: tensor too large (32-bit buffer offsets)");
-    a.M = B * a.Ho * a.Wo;
+    const bool c64 = Cin % 64 == 0 && a.Cin1 % 64 == 0;                       // what the row-reuse and two-group kernels take
     hipStream_t st = (hipStream_t)stream;
     // tile_hint 0: the two-group kernel takes the layers it measures faster on (r03, profiles/r03/e_bench_conv_two_group.jsonl): 3 x 3 / stride 1 layers
     // whose 256-pixel tiles are whole image rows, from 64 x 64 upwards (row-reuse form), and the upsampling convolution of the 128 x 128 level
-    static const bool pp_auto = getenv("SSDNERF_CONV_NO_TWO_GROUP") == nullptr;
-    if (tile_hint == 0 && pp_auto && c64 && Cout % 128 == 0 && ksize == 3 && stride == 1 && a.M >= 32768 && (!gn_sums || (a.Ho * a.Wo) % 256 == 0)
+    if (tile_hint == 0 && c64 && Cout % 128 == 0 && ksize == 3 && stride == 1 && a.M >= 32768 && (!gn_sums || (a.Ho * a.Wo) % 256 == 0)
         && ((!upsample && (W == 128 || W == 64) && (H * W) % 256 == 0) || (upsample && a.M >= 131072)))
         tile_hint = 6;
     if (tile_hint == 5 || tile_hint == 6) {                                  // two-group ("ping-pong") 256 x 128 kernel; 6: the row-reuse form where it applies
         SSD_REQUIRE(c64 && Cout % 128 == 0, "conv2d_nhwc_bf16: the 256 x 128 kernel needs Cin %% 64 == 0 and Cout %% 128 == 0");
         SSD_REQUIRE(!gn_sums || (a.Ho * a.Wo) % 256 == 0, "conv2d_nhwc_bf16: fused GroupNorm statistics need Ho*Wo to be a multiple of the M tile");
-        a.splits = 1;
 #ifdef CV_PP_TIMING
         a.splitk_ws = (float*)splitk_ws;                                     // instrumented build: the caller's scratch receives the time stamps
-#else
-        a.splitk_ws = nullptr;
 #endif
-        a.m_tiles = (a.M + 255) / 256; a.n_tiles = Cout / 128;
         const bool pp_rows = tile_hint == 6 && ksize == 3 && stride == 1 && !upsample && (W == 128 || W == 64 || W == 32) && (H * W) % 256 == 0;
-        static int n_cu = 0;                                                 // one block per CU (LDS), persistent over the tiles
-        if (n_cu == 0) {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cu = prop.multiProcessorCount;
-            if (n_cu < 8) n_cu = 256;
-            n_cu &= ~7;
-        }
-        const uint32_t tiles = a.m_tiles * a.n_tiles, grid = tiles < (uint32_t)n_cu ? tiles : (uint32_t)n_cu;
-        if (pp_rows) hipLaunchKernelGGL((k_conv_pp_bf16<true>), dim3(grid), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_conv_pp_bf16<false>), dim3(grid), dim3(512), 0, st, a);
+        if (pp_rows) cv_launch_pp<true>(a, st); else cv_launch_pp<false>(a, st);
         SSD_CHECK_LAUNCH("conv2d_nhwc_bf16");
         return SSDNERF_OK;
     }
     int choice; uint32_t splits;
-    cv_plan(a.M, Cin, Cout, ksize, tile_hint, splitk_ws && splitk_ws_bytes >= (size_t)a.M * Cout * 4 && Cout <= 1024, splits_hint, &choice, &splits);
+    cv_plan(a.M, Cin, Cout, ksize, tile_hint, a.splitk_ws && Cout <= 1024, splits_hint, &choice, &splits);
     if (choice != 3) SSD_REQUIRE(Cout % 128 == 0, "conv2d_nhwc_bf16: 128-wide tiles need Cout %% 128 == 0");
     SSD_REQUIRE(!gn_sums || splits > 1 || (a.Ho * a.Wo) % (choice == 4 ? 256 : choice == 1 ? 128 : 64) == 0, "conv2d_nhwc_bf16: fused GroupNorm statistics need Ho*Wo to be a multiple of the M tile");
-    a.splits = splits; a.splitk_ws = (float*)splitk_ws;
-    double* stats = a.gn_sums;
-    a.tickets = nullptr;
-    if (splits > 1) {
-        const uint32_t bm = choice == 4 ? 256 : choice == 1 ? 128 : 64, bn = choice == 3 ? 64 : 128;
-        a.m_tiles = (a.M + bm - 1) / bm; a.n_tiles = (Cout + bn - 1) / bn;     // (what cv_launch sets; the fold needs the tile count now)
-        a.tickets = cv_fold_tickets(a, splitk_ws, splitk_ws_bytes, bm, stats != nullptr);
-        if (!a.tickets) a.gn_sums = nullptr;                                 // a split layer's statistics are taken by the finishing pass, or -- folded -- by the last block's epilogue
-    }
-    static const bool rows_ok = getenv("SSDNERF_CONV_NO_ROW_REUSE") == nullptr;
-    const bool rows = rows_ok && c64 && choice == 1 && splits == 1 && ksize == 3 && stride == 1 && !upsample && (W == 128 || W == 64 || W == 32) && (H * W) % 128 == 0;
+    a.splits = splits;
+    const bool rows = c64 && choice == 1 && splits == 1 && ksize == 3 && stride == 1 && !upsample && (W == 128 || W == 64 || W == 32) && (H * W) % 128 == 0;
     if (rows) {
         a.m_tiles = (a.M + 127) / 128; a.n_tiles = Cout / 128;
         hipLaunchKernelGGL(k_conv3x3_bf16_rows, dim3(a.m_tiles * a.n_tiles), dim3(256), 0, st, a);
     } else if (choice == 4) cv_launch<2, 2, 4, 2, 3>(a, st); else if (choice == 1) cv_launch<2, 2, 2, 2, 2>(a, st); else if (choice == 2) cv_launch<1, 2, 2, 2, 3>(a, st); else cv_launch<1, 1, 2, 2, CV_NS_SMALL>(a, st);
-    if (splits > 1 && !a.tickets) {
-        const uint32_t HWo = a.Ho * a.Wo, cpr = Cout / 8, rstep = 256 / cpr ? 256 / cpr : 1;
-        uint32_t rows = HWo;                                                 // rows per block: >= one pass of the rows in flight, ~1024 blocks
-        while (rows > rstep && rows % 2 == 0 && (uint64_t)B * (HWo / rows) < 1024) rows /= 2;
-        hipLaunchKernelGGL(k_conv_splitk_finish, dim3((HWo + rows - 1) / rows, B), dim3(256), 0, st, a.splitk_ws, bias, a.res, a.y, HWo, cpr, rows, stats, a.G);
-    }
+    if (splits > 1) cv_launch_finish(a, false, a.splitk_ws, st);
     SSD_CHECK_LAUNCH("conv2d_nhwc_bf16");
     return SSDNERF_OK;
 }

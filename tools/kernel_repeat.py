@@ -23,7 +23,6 @@ for (H, Cin, Cout, k) in ((128, 128, 128, 3), (64, 256, 256, 3), (64, 512, 256, 
     bias = torch.randn(Cout, device="cuda")
     w_hi, w_lo = [t.contiguous(memory_format=torch.channels_last) for t in UF.split_bf16x2(w)]
     for hint, tag in ((0, "auto"), (1, "generic 128x128")):
-        os.environ.pop("SSDNERF_CONV_NO_ROW_REUSE", None)
         repeat(f"conv fp32-class {Cin}->{Cout} k{k} @{H} [{tag}]", lambda: UF.conv2d_nhwc_f32x2(x, w_hi, w_lo, bias, None, 1, False, tile_hint=hint, splits_hint=1))
         x16, w16 = x.bfloat16().contiguous(memory_format=torch.channels_last), w.bfloat16().contiguous(memory_format=torch.channels_last)
         repeat(f"conv bf16 {Cin}->{Cout} k{k} @{H} [{tag}]", lambda: UF.conv2d_nhwc_bf16(x16, w16, bias, None, 1, False, tile_hint=hint, splits_hint=1))
