@@ -287,6 +287,17 @@ int ssdnerf_cam_rays(const float* c2w, const float* intrinsics, uint32_t n_views
 /* y[i] = uint8(round_half_even(clamp(x[i], 0, 1) * 255)): the output quantisation of eval_and_viz (base_nerf.py:551-553). */
 int ssdnerf_quantize_u8(const float* x, uint64_t n, uint8_t* y, void* stream);
 
+/* Test-view scores (eval_psnr / eval_ssim_skimage, lib/core/evaluation/metrics.py:52-71, as eval_and_viz calls them) of n image pairs
+ * a, b [n][h][w][3] fp32, channel-last and contiguous, in one launch:
+ *   mse[i]  = mean over h*w*3 of (a - b)^2, accumulated in fp64;
+ *   ssim[i] = skimage.metrics.structural_similarity(channel_axis=-1, data_range=1), skimage >= 0.19 defaults: per channel, 7 x 7 uniform
+ *             window means u* of x, y, x^2, y^2, xy; vx = 49/48 (uxx - ux^2), vy = 49/48 (uyy - uy^2), vxy = 49/48 (uxy - ux uy);
+ *             S = (2 ux uy + C1)(2 vxy + C2) / ((ux^2 + uy^2 + C1)(vx + vy + C2)), C1 = 0.01^2, C2 = 0.03^2; the channel value is the mean of
+ *             S over rows [3, h-4] x columns [3, w-4] (the pixels whose window lies inside the image); ssim[i] is the mean of the 3 channels.
+ * Window sums and vx, vy, vxy are formed in fp64.  No atomics, a fixed reduction order: bit-identical from run to run.
+ * Null pointers, n == 0, h < 7 or w < 7 fail with SSDNERF_E_INVALID before any HIP call. */
+int ssdnerf_image_metrics(const float* a, const float* b, uint32_t n, uint32_t h, uint32_t w, float* mse, float* ssim, void* stream);
+
 /* ---- Part 3: denoising-UNet glue (lib/models/architecture/ddpm/modules.py:12-129, denoising.py:178-187) ------------------
  * Activations are channel-last: x, y are [B][HW][C] of dtype 0 = fp32, 1 = fp16, 2 = bf16.
  *

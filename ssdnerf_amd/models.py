@@ -29,6 +29,7 @@ from .codes import attr_path_get, attr_path_set, frozen
 from .codes import IdentityCode, MSELoss, NormalizedTanhCode, RegLoss, TanhCode  # noqa: F401  (registered here for config builds)
 from .density import get_density as _get_density, update_density_grid
 from .fitting import CodeFitter, Conditioning, GuidanceObjective, RayBatcher
+from .metrics import image_metrics
 from .registry import MODELS, build_module, get_module_device
 
 
@@ -630,11 +631,21 @@ class DiffusionNeRF(MultiSceneNeRF):
         raise AttributeError(f"cond_mode={mode!r}")
 
     def val_step(self, data, **kwargs):
+        """Scene codes for the batch, and its ``test_poses`` rendered and quantised to k/255 (``pred_imgs``, (S, V, 3, h, w)).  As ``eval_and_viz``
+        (base_nerf.py:535-558): with ``test_imgs`` (S, V, h, w, 3) in the batch and ``test_cfg['skip_eval']`` unset, the views are rendered at the
+        ground truth's size and scored against it -- ``log_vars`` holds ``test_psnr`` / ``test_ssim``, the means over all views, and ``test_metrics``
+        the per-view values as (S, V) device tensors (metrics.image_metrics).  LPIPS is not computed."""
         with torch.no_grad():
             code, grid, bits = self._scene_from(data, kwargs)
-            pred = None
+            pred, log_vars, extra = None, dict(), dict()
             if "test_poses" in data:
-                h, w = self.test_cfg.get("img_size", (128, 128))
+                evaluate = "test_imgs" in data and not self.test_cfg.get("skip_eval", False)
+                h, w = data["test_imgs"].shape[2:4] if evaluate else self.test_cfg.get("img_size", (128, 128))
                 image, _ = self.render(self._modules_for_eval(), code, bits, h, w, data["test_intrinsics"], data["test_poses"], cfg=self.test_cfg)
-                pred = (torch.round(image.clamp(0, 1) * 255) / 255).permute(0, 1, 4, 2, 3)
-        return dict(log_vars=dict(), num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits)
+                image = torch.round(image.clamp(0, 1) * 255) / 255
+                if evaluate:
+                    psnr, ssim = image_metrics(image, data["test_imgs"].to(image.device, torch.float32))
+                    log_vars = dict(test_psnr=float(psnr.mean()), test_ssim=float(ssim.mean()))
+                    extra["test_metrics"] = dict(psnr=psnr, ssim=ssim)
+                pred = image.permute(0, 1, 4, 2, 3)
+        return dict(log_vars=log_vars, num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits, **extra)

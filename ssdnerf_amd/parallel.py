@@ -80,6 +80,20 @@ def weighted_log_vars(log_vars: dict, batch_sizes: List[int], device=None) -> di
     return out
 
 
+def evaluate_3d(model, batches, **sample_kwargs) -> dict:
+    """The scene-parallel evaluation loop of lib/apis/test.py:12-73, without the FID / IS feeding, the visualisation and the progress bar:
+    ``model.val_step(data, **sample_kwargs)`` on every batch of THIS rank (``batches``: an iterable of batch dicts, e.g. this rank's data
+    loader), then every logged scalar (``test_psnr``, ``test_ssim``) averaged over all scenes of all ranks by ``weighted_log_vars``."""
+    log_vars, batch_sizes = {}, []
+    for data in batches:
+        out = model.val_step(data, **sample_kwargs)
+        for key, value in out["log_vars"].items():
+            log_vars.setdefault(key, []).append(value)
+        batch_sizes.append(out["num_samples"])
+    nccl = dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl"
+    return weighted_log_vars(log_vars, batch_sizes, device=torch.device("cuda", torch.cuda.current_device()) if nccl else None)
+
+
 # ---------------------------------------------------------------------------------------------- second axis: views (SURVEY.md section 8(e): "#scenes < #GPUs")
 def plan_render_shards(num_scenes: int, num_views: int, world_size: int) -> List[Tuple[int, int, int, int]]:
     """Per rank ``(scene_lo, scene_hi, view_lo, view_hi)`` of a render of ``num_scenes`` scenes x ``num_views`` views on ``world_size`` ranks.
