@@ -81,13 +81,20 @@ SSD_DEV uint32_t cv_pack_bf16(float lo, float hi) {
 // v_permlane32_swap per packed dword pairs the two lane halves so that every lane holds 8 consecutive channels, and the tile leaves as 16-byte stores
 // (programming guide T21).  No LDS round trip, no block barrier: the LDS-staged epilogue above cost 17 - 25 us of a 56 us layer once the K loop no
 // longer hid it (profiles/r03/d_pp_epilogue_split.txt).  GroupNorm sums of the rounded values: per lane over its pixels, DPP-reduced over the 32
-// lanes of each half, one LDS atomic per 4-channel run and wave, then the same per-group fp64 atomics as cv_epilogue_bf16.
-SSD_DEV float cv_half_wave_sum(float v) {                                       // sum over the 32 lanes of each wave half, valid in lanes 16-31 / 48-63
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xf, 0xf, true));    // quad_perm [1,0,3,2]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x4E, 0xf, 0xf, true));    // quad_perm [2,3,0,1]
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x141, 0xf, 0xf, true));   // row_half_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x140, 0xf, 0xf, true));   // row_mirror
-    v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x142, 0xa, 0xf, false));  // row_bcast:15 into rows 1 and 3
+// lanes of each half, one LDS atomic per 4-channel run and wave, then the same per-group fp64 atomics as cv_epilogue_bf16 -- all in fp64 from the
+// first add: the consumer forms E[x^2] - E[x]^2, which fp32 partial sums lose at a large group mean.
+template <int CTRL, int RM, int BM, bool BC> SSD_DEV double cv_dpp_f64(double v) {                // one DPP move of an fp64 value (two dword moves)
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTRL, RM, BM, BC);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTRL, RM, BM, BC);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+SSD_DEV double cv_half_wave_sum(double v) {                                     // sum over the 32 lanes of each wave half, valid in lanes 16-31 / 48-63
+    v += cv_dpp_f64<0xB1, 0xf, 0xf, true>(v);
+    v += cv_dpp_f64<0x4E, 0xf, 0xf, true>(v);
+    v += cv_dpp_f64<0x141, 0xf, 0xf, true>(v);
+    v += cv_dpp_f64<0x140, 0xf, 0xf, true>(v);
+    v += cv_dpp_f64<0x142, 0xa, 0xf, false>(v);
     return v;
 }
 
@@ -95,10 +102,11 @@ template <int TM, int TN, bool F32 = false>
 SSD_DEV void cv_epilogue_direct(const ConvArgs& a, f32x16 (&acc)[TN][TM], unsigned char* lds, uint32_t m0, uint32_t n0, uint32_t wm, uint32_t wn) {
     constexpr int BN = 128;
     const uint32_t tid = threadIdx.x, lane = tid & 63, half = lane >> 5;
-    float* red = reinterpret_cast<float*>(lds);                              // [BN / 4 runs][sum, sumsq]: the caller hands in 512 bytes BEHIND the stage ring (the
+    using S = double;                                                        // statistics in fp64 from the first add (the consumer forms E[x^2] - E[x]^2)
+    S* red = reinterpret_cast<S*>(lds);                                      // [BN / 4 runs][sum, sumsq]: the caller hands in 512 bytes BEHIND the stage ring (the
                                                                              // persistent kernel's zero rows at the head of A stage 0 must survive this epilogue)
     if (a.gn_sums) {
-        if (tid < BN / 4 * 2) red[tid] = 0.f;
+        if (tid < BN / 4 * 2) red[tid] = S(0);
         __syncthreads();
     }
 #pragma unroll
@@ -107,7 +115,7 @@ SSD_DEV void cv_epilogue_direct(const ConvArgs& a, f32x16 (&acc)[TN][TM], unsign
         float4 bv[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) bv[q] = a.bias ? *reinterpret_cast<const float4*>(a.bias + cb + 8 * q + 4 * half) : make_float4(0.f, 0.f, 0.f, 0.f);
-        float gs[4] = {0.f, 0.f, 0.f, 0.f}, gq[4] = {0.f, 0.f, 0.f, 0.f};
+        S gs[4] = {S(0), S(0), S(0), S(0)}, gq[4] = {S(0), S(0), S(0), S(0)};
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
             const uint32_t m = m0 + wm * 32 * TM + i * 32 + (lane & 31);
@@ -125,9 +133,8 @@ SSD_DEV void cv_epilogue_direct(const ConvArgs& a, f32x16 (&acc)[TN][TM], unsign
                     }
                     if (ok) *reinterpret_cast<float4*>(reinterpret_cast<float*>(a.y) + o) = make_float4(f[0], f[1], f[2], f[3]);
                     if (a.gn_sums && ok) {
-                        gs[q] += (f[0] + f[1]) + (f[2] + f[3]);
-                        gq[q] = __builtin_fmaf(f[0], f[0], gq[q]); gq[q] = __builtin_fmaf(f[1], f[1], gq[q]);
-                        gq[q] = __builtin_fmaf(f[2], f[2], gq[q]); gq[q] = __builtin_fmaf(f[3], f[3], gq[q]);
+#pragma unroll
+                        for (int k = 0; k < 4; ++k) { const double v = f[k]; gs[q] += v; gq[q] = __builtin_fma(v, v, gq[q]); }
                     }
                     continue;
                 }
@@ -138,11 +145,10 @@ SSD_DEV void cv_epilogue_direct(const ConvArgs& a, f32x16 (&acc)[TN][TM], unsign
                 }
                 pk[q] = make_uint2(cv_pack_bf16(f[0], f[1]), cv_pack_bf16(f[2], f[3]));
                 if (a.gn_sums && ok) {
-                    const float r0 = __uint_as_float(pk[q].x << 16), r1 = __uint_as_float(pk[q].x & 0xffff0000u);
-                    const float r2 = __uint_as_float(pk[q].y << 16), r3 = __uint_as_float(pk[q].y & 0xffff0000u);
-                    gs[q] += (r0 + r1) + (r2 + r3);
-                    gq[q] = __builtin_fmaf(r0, r0, gq[q]); gq[q] = __builtin_fmaf(r1, r1, gq[q]);
-                    gq[q] = __builtin_fmaf(r2, r2, gq[q]); gq[q] = __builtin_fmaf(r3, r3, gq[q]);
+                    const double r[4] = {__uint_as_float(pk[q].x << 16), __uint_as_float(pk[q].x & 0xffff0000u), __uint_as_float(pk[q].y << 16),
+                                         __uint_as_float(pk[q].y & 0xffff0000u)};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) { gs[q] += r[k]; gq[q] = __builtin_fma(r[k], r[k], gq[q]); }
                 }
             }
 #pragma unroll
@@ -155,7 +161,7 @@ SSD_DEV void cv_epilogue_direct(const ConvArgs& a, f32x16 (&acc)[TN][TM], unsign
         if (a.gn_sums) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const float s1 = cv_half_wave_sum(gs[q]), s2 = cv_half_wave_sum(gq[q]);
+                const S s1 = cv_half_wave_sum(gs[q]), s2 = cv_half_wave_sum(gq[q]);
                 if ((lane & 31) == 31) {                                     // lanes 31 and 63 hold their half's totals: run index = (channel - n0) / 4
                     const uint32_t run = (cb - n0 + 8 * q + 4 * half) / 4;
                     atomicAdd(&red[run * 2], s1);
@@ -169,7 +175,7 @@ SSD_DEV void cv_epilogue_direct(const ConvArgs& a, f32x16 (&acc)[TN][TM], unsign
         const uint32_t cpg = a.Cout / a.G, hpg = cpg / 4, g0 = n0 / cpg, ng = (n0 + BN - 1) / cpg - g0 + 1;
         if (tid < ng && m0 < a.M) {
             const uint32_t lo = max((g0 + tid) * hpg, n0 / 4) - n0 / 4, hi = min((g0 + tid + 1) * hpg, (n0 + BN) / 4) - n0 / 4;
-            float ss = 0.f, qq = 0.f;
+            S ss = S(0), qq = S(0);
             for (uint32_t i = lo; i < hi; ++i) { ss += red[i * 2]; qq += red[i * 2 + 1]; }
             double* dst = a.gn_sums + ((size_t)(m0 / (a.Ho * a.Wo)) * a.G + g0 + tid) * 2;
             atomicAdd(dst, (double)ss);
@@ -204,14 +210,14 @@ SSD_DEV void cv_epilogue_bf16(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave / WN, wn = wave % WN;
     float* tile_f = reinterpret_cast<float*>(lds);
     constexpr int CPR = BN / 8;                                              // 8-channel chunks per row; NT % CPR == 0, so a thread keeps its chunk column
-    float* red = reinterpret_cast<float*>(lds + EPI);                        // [CPR][2 halves][sum, sumsq] block partials for the GroupNorm statistics
-    if (a.gn_sums && tid < CPR * 4) red[tid] = 0.f;
+    double* red = reinterpret_cast<double*>(lds + EPI);                      // [CPR][2 halves][sum, sumsq] block partials for the GroupNorm statistics (fp64
+    if (a.gn_sums && tid < CPR * 4) red[tid] = 0.0;                          // from the first add, as cv_epilogue_f32; CPR * 4 doubles: the 512 bytes behind EPI)
     const uint32_t cc = tid % CPR, co = n0 + cc * 8;
     const bool c_ok = !PT || co < a.Cout;                                    // (PT: Cout is a multiple of 8 and need not fill the last N tile)
     float bias_v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) bias_v[k] = (a.bias && c_ok) ? a.bias[co + k] : 0.f;
-    float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};
+    double gs[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};
 #pragma unroll
     for (int pass = 0; pass < BM / EP_ROWS; ++pass) {
         if (pass) __syncthreads();                                           // the previous pass has been read out
@@ -251,10 +257,10 @@ SSD_DEV void cv_epilogue_bf16(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned
             if (a.gn_sums) {                                                 // statistics of what the next norm will read (the rounded values)
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float lo = __uint_as_float(pk[k] << 16), hi = __uint_as_float(pk[k] & 0xffff0000u);
+                    const double lo = __uint_as_float(pk[k] << 16), hi = __uint_as_float(pk[k] & 0xffff0000u);
                     gs[k >> 1] += lo + hi;
-                    gq[k >> 1] = __builtin_fmaf(lo, lo, gq[k >> 1]);
-                    gq[k >> 1] = __builtin_fmaf(hi, hi, gq[k >> 1]);
+                    gq[k >> 1] = __builtin_fma(lo, lo, gq[k >> 1]);
+                    gq[k >> 1] = __builtin_fma(hi, hi, gq[k >> 1]);
                 }
             }
         }
@@ -268,11 +274,11 @@ SSD_DEV void cv_epilogue_bf16(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned
         if (tid < ng && m0 < a.M) {
             // half chunks of group g0 + tid inside this tile: global half-chunk index range [g*hpg, (g+1)*hpg) minus the tile's first, n0/4
             const uint32_t lo = max((g0 + tid) * hpg, n0 / 4) - n0 / 4, hi = min((g0 + tid + 1) * hpg, n1 / 4) - n0 / 4;
-            float ss = 0.f, qq = 0.f;
+            double ss = 0.0, qq = 0.0;
             for (uint32_t i = lo; i < hi; ++i) { ss += red[i * 2]; qq += red[i * 2 + 1]; }
             double* dst = a.gn_sums + ((size_t)(m0 / (a.Ho * a.Wo)) * a.G + g0 + tid) * 2;
-            atomicAdd(dst, (double)ss);
-            atomicAdd(dst + 1, (double)qq);
+            atomicAdd(dst, ss);
+            atomicAdd(dst + 1, qq);
         }
     }
 }
@@ -505,15 +511,15 @@ SSD_DEV void cv_epilogue_f32(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned 
             for (int e = 0; e < 16; ++e)
                 tile_f[(wm * 32 * TM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)) * BN + wn * 32 * TN + j * 32 + (lane & 31)] = acc[i][j][e];
     constexpr int CPR = BN / 8;
-    float* red = reinterpret_cast<float*>(lds + EPI);
-    if (a.gn_sums && tid < CPR * 4) red[tid] = 0.f;
+    double* red = reinterpret_cast<double*>(lds + EPI);                      // CPR * 4 doubles: the 512 bytes behind the tile
+    if (a.gn_sums && tid < CPR * 4) red[tid] = 0.0;
     __syncthreads();
     const uint32_t cc = tid % CPR, co = n0 + cc * 8;
     const bool c_ok = !PT || co < a.Cout;
     float bias_v[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) bias_v[k] = (a.bias && c_ok) ? a.bias[co + k] : 0.f;
-    float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};
+    double gs[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};                           // fp64 from the first add (the consumer forms E[x^2] - E[x]^2)
     float* yo = reinterpret_cast<float*>(a.y);
     const float* ro = reinterpret_cast<const float*>(a.res);
 #pragma unroll 2
@@ -533,7 +539,7 @@ SSD_DEV void cv_epilogue_f32(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned 
         *reinterpret_cast<float4*>(yo + o + 4) = make_float4(f[4], f[5], f[6], f[7]);
         if (a.gn_sums) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { gs[k >> 2] += f[k]; gq[k >> 2] = __builtin_fmaf(f[k], f[k], gq[k >> 2]); }
+            for (int k = 0; k < 8; ++k) { const double v = f[k]; gs[k >> 2] += v; gq[k >> 2] = __builtin_fma(v, v, gq[k >> 2]); }
         }
     }
     if (a.gn_sums) {
@@ -544,11 +550,11 @@ SSD_DEV void cv_epilogue_f32(const ConvArgs& a, f32x16 (&acc)[TM][TN], unsigned 
         const uint32_t cpg = a.Cout / a.G, hpg = cpg / 4, g0 = n0 / cpg, ng = (n1 - 1) / cpg - g0 + 1;
         if (tid < ng && m0 < a.M) {
             const uint32_t lo = max((g0 + tid) * hpg, n0 / 4) - n0 / 4, hi = min((g0 + tid + 1) * hpg, n1 / 4) - n0 / 4;
-            float ss = 0.f, qq = 0.f;
+            double ss = 0.0, qq = 0.0;
             for (uint32_t i = lo; i < hi; ++i) { ss += red[i * 2]; qq += red[i * 2 + 1]; }
             double* dst = a.gn_sums + ((size_t)(m0 / (a.Ho * a.Wo)) * a.G + g0 + tid) * 2;
-            atomicAdd(dst, (double)ss);
-            atomicAdd(dst + 1, (double)qq);
+            atomicAdd(dst, ss);
+            atomicAdd(dst + 1, qq);
         }
     }
 }
@@ -1072,14 +1078,14 @@ __global__ __launch_bounds__(256) void k_conv3x3_f32x2_rows(const ConvArgs a, co
 // the zero fill of y in front of every split layer -- 46 fill kernels per forward) goes back to zero.  Same thread layout as k_conv_splitk_finish.
 __global__ __launch_bounds__(256) void k_conv_f32_finish(float* __restrict__ y, float* __restrict__ ws, const float* __restrict__ bias, const float* __restrict__ res, uint32_t HW,
                                                          uint32_t cpr, uint32_t rows_per_block, double* __restrict__ gn_sums, uint32_t G) {
-    __shared__ float red[512];
+    __shared__ double red[512];                                              // fp64 from the first add, as cv_epilogue_f32
     const uint32_t tid = threadIdx.x, cc = tid % cpr, rstep = 256 / cpr, b = blockIdx.y;
     const uint32_t Cout = cpr * 8, co = cc * 8;
-    if (gn_sums) { for (uint32_t i = tid; i < cpr * 4; i += 256) red[i] = 0.f; __syncthreads(); }
+    if (gn_sums) { for (uint32_t i = tid; i < cpr * 4; i += 256) red[i] = 0.0; __syncthreads(); }
     float bv[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) bv[k] = bias ? bias[co + k] : 0.f;
-    float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};
+    double gs[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};
     const uint32_t row_end = (tid / cpr < rstep) ? min((blockIdx.x + 1) * rows_per_block, HW) : 0u;
     for (uint32_t row = blockIdx.x * rows_per_block + tid / cpr; row < row_end; row += rstep) {
         const size_t o = (((size_t)b * HW + row) * cpr + cc) * 8;
@@ -1097,7 +1103,7 @@ __global__ __launch_bounds__(256) void k_conv_f32_finish(float* __restrict__ y, 
         *reinterpret_cast<float4*>(y + o + 4) = make_float4(f[4], f[5], f[6], f[7]);
         if (gn_sums) {
 #pragma unroll
-            for (int k = 0; k < 8; ++k) { gs[k >> 2] += f[k]; gq[k >> 2] = __builtin_fmaf(f[k], f[k], gq[k >> 2]); }
+            for (int k = 0; k < 8; ++k) { const double v = f[k]; gs[k >> 2] += v; gq[k >> 2] = __builtin_fma(v, v, gq[k >> 2]); }
         }
     }
     if (gn_sums) {
@@ -1106,11 +1112,11 @@ __global__ __launch_bounds__(256) void k_conv_f32_finish(float* __restrict__ y, 
         __syncthreads();
         const uint32_t hpg = (Cout / G) / 4;
         for (uint32_t g = tid; g < G; g += 256) {
-            float ss = 0.f, qq = 0.f;
+            double ss = 0.0, qq = 0.0;
             for (uint32_t i = g * hpg; i < (g + 1) * hpg; ++i) { ss += red[i * 2]; qq += red[i * 2 + 1]; }
             double* dst = gn_sums + ((size_t)b * G + g) * 2;
-            atomicAdd(dst, (double)ss);
-            atomicAdd(dst + 1, (double)qq);
+            atomicAdd(dst, ss);
+            atomicAdd(dst + 1, qq);
         }
     }
 }
@@ -1120,14 +1126,14 @@ __global__ __launch_bounds__(256) void k_conv_f32_finish(float* __restrict__ y, 
 __global__ __launch_bounds__(256) void k_conv_splitk_finish(float* __restrict__ ws, const float* __restrict__ bias, const unsigned char* __restrict__ res,
                                                             unsigned char* __restrict__ y, uint32_t HW, uint32_t cpr, uint32_t rows_per_block,
                                                             double* __restrict__ gn_sums, uint32_t G) {
-    __shared__ float red[512];                                               // [cpr][2 halves][sum, sumsq], cpr <= 64... sized for Cout <= 1024
+    __shared__ double red[512];                                              // [cpr][2 halves][sum, sumsq], cpr <= 64... sized for Cout <= 1024 (fp64 from the first add)
     const uint32_t tid = threadIdx.x, cc = tid % cpr, rstep = 256 / cpr, b = blockIdx.y;      // threads past rstep * cpr idle (cpr not a divisor of 256)
     const uint32_t Cout = cpr * 8, co = cc * 8;
-    if (gn_sums) { for (uint32_t i = tid; i < cpr * 4; i += 256) red[i] = 0.f; __syncthreads(); }
+    if (gn_sums) { for (uint32_t i = tid; i < cpr * 4; i += 256) red[i] = 0.0; __syncthreads(); }
     float bv[8];
 #pragma unroll
     for (int k = 0; k < 8; ++k) bv[k] = bias ? bias[co + k] : 0.f;
-    float gs[2] = {0.f, 0.f}, gq[2] = {0.f, 0.f};
+    double gs[2] = {0.0, 0.0}, gq[2] = {0.0, 0.0};
     const uint32_t row_end = (tid / cpr < rstep) ? min((blockIdx.x + 1) * rows_per_block, HW) : 0u;
     for (uint32_t row = blockIdx.x * rows_per_block + tid / cpr; row < row_end; row += rstep) {
         const size_t q = ((size_t)b * HW + row) * cpr + cc;
@@ -1150,10 +1156,10 @@ __global__ __launch_bounds__(256) void k_conv_splitk_finish(float* __restrict__ 
         if (gn_sums) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const float lo = __uint_as_float(pk[k] << 16), hi = __uint_as_float(pk[k] & 0xffff0000u);
+                const double lo = __uint_as_float(pk[k] << 16), hi = __uint_as_float(pk[k] & 0xffff0000u);
                 gs[k >> 1] += lo + hi;
-                gq[k >> 1] = __builtin_fmaf(lo, lo, gq[k >> 1]);
-                gq[k >> 1] = __builtin_fmaf(hi, hi, gq[k >> 1]);
+                gq[k >> 1] = __builtin_fma(lo, lo, gq[k >> 1]);
+                gq[k >> 1] = __builtin_fma(hi, hi, gq[k >> 1]);
             }
         }
     }
@@ -1163,11 +1169,11 @@ __global__ __launch_bounds__(256) void k_conv_splitk_finish(float* __restrict__ 
         __syncthreads();
         const uint32_t hpg = (Cout / G) / 4;                                 // 4-channel half chunks per group: one pair of atomics per group and block
         for (uint32_t g = tid; g < G; g += 256) {
-            float ss = 0.f, qq = 0.f;
+            double ss = 0.0, qq = 0.0;
             for (uint32_t i = g * hpg; i < (g + 1) * hpg; ++i) { ss += red[i * 2]; qq += red[i * 2 + 1]; }
             double* dst = gn_sums + ((size_t)b * G + g) * 2;
-            atomicAdd(dst, (double)ss);
-            atomicAdd(dst + 1, (double)qq);
+            atomicAdd(dst, ss);
+            atomicAdd(dst + 1, qq);
         }
     }
 }

@@ -114,11 +114,46 @@ constexpr int GN_MAX_C = 2048;
 // convolution that produced x, added on load so that the producer does not need a pass of its own for it.
 // x may be the channel concatenation [x | x2] of two tensors (C1 channels from x, C - C1 from x2) that is never materialised: the
 // skip connections of the UNet's decoder half (denoising.py:209-213 `torch.cat([h, hs.pop()], dim=1)`).
+// Block partials of the statistics -> per (sample, group) fp64 atomics, for ONE of the two sums (x or x^2): `v` holds a thread's fp64 sums for its V
+// channels, `part` [row-in-flight][C] doubles (the caller's LDS; the same bytes as the fp32 pair of arrays it replaced), `dst` = &sums[b][0][which].
+// Every thread of the block calls it (barriers inside).
+template <int V>
+__device__ __forceinline__ void gn_fold_to_groups(double* part, const double (&v)[V], bool active, uint32_t lane_row, uint32_t cv, uint32_t rif, uint32_t C,
+                                                  uint32_t G, double* __restrict__ dst) {
+    if (active) {
+#pragma unroll
+        for (int i = 0; i < V; ++i) part[lane_row * C + cv * V + i] = v[i];
+    }
+    __syncthreads();
+    for (uint32_t c = threadIdx.x; c < C; c += GN_TPB) {                   // fold the rows-in-flight, result in row 0
+        double t = 0.0;
+        for (uint32_t r = 0; r < rif; ++r) t += part[r * C + c];
+        part[c] = t;                                                       // row 0 slot c is only read by this thread above
+    }
+    __syncthreads();
+    const uint32_t cpg = C / G;
+    for (uint32_t g = threadIdx.x; g < G; g += GN_TPB) {
+        double t = 0.0;
+        for (uint32_t i = 0; i < cpg; ++i) t += part[g * cpg + i];
+        atomicAdd(&dst[(size_t)g * 2], t);
+    }
+    __syncthreads();                                                       // (part is refilled by the next call)
+}
+
+// grid (HW / rows_per_block, B).  Threads are laid out [row-in-flight][channel vector]; a thread keeps V running sums for
+// its fixed channel vector, the block folds them over the rows in flight through LDS (conflict-free: consecutive threads,
+// consecutive channels), then per group, then adds to the global fp64 sums.  pre_bias (nullable, fp32 [C]) is the bias of the
+// convolution that produced x, added on load so that the producer does not need a pass of its own for it.
+// x may be the channel concatenation [x | x2] of two tensors (C1 channels from x, C - C1 from x2) that is never materialised: the
+// skip connections of the UNet's decoder half (denoising.py:209-213 `torch.cat([h, hs.pop()], dim=1)`).
+// The sums are fp64 from the first add: the square of an fp32 value is exact in fp64, and the consumer forms E[x^2] - E[x]^2, which loses
+// (|mean| / std)^2 times the relative error of the sums -- fp32 partial sums cost the fp32 path its accuracy at |mean| / std ~ 100
+// (tests/test_unet_kernels_fp64_gpu.py, offsets).
 template <int DT>
 __global__ __launch_bounds__(GN_TPB) void k_gn_stats(const void* __restrict__ x, const void* __restrict__ x2, uint32_t C1, const float* __restrict__ pre_bias,
                                                       uint32_t HW, uint32_t C, uint32_t G, uint32_t rows_per_block, double* __restrict__ sums) {
     constexpr int V = GnVec<DT>::V;
-    __shared__ float part_s[GN_TPB * V], part_q[GN_TPB * V];              // [row-in-flight][C]  (rif * C <= 256 * V)
+    __shared__ double part[GN_TPB * V];                                    // [row-in-flight][C]  (rif * C <= 256 * V)
     const uint32_t tpr = C / V, rif = GN_TPB / tpr;
     const uint32_t lane_row = threadIdx.x / tpr, cv = threadIdx.x % tpr;
     const uint32_t b = blockIdx.y, row0 = blockIdx.x * rows_per_block;
@@ -126,34 +161,25 @@ __global__ __launch_bounds__(GN_TPB) void k_gn_stats(const void* __restrict__ x,
     const bool second = cv >= tpr1;
     const void* src = second ? x2 : x;
     const uint32_t stpr = second ? tpr - tpr1 : tpr1, scv = second ? cv - tpr1 : cv;
-    if (lane_row < rif) {
-        float s[V], q[V], pb[V];
+    double s[V], q[V];
 #pragma unroll
-        for (int i = 0; i < V; ++i) { s[i] = 0.f; q[i] = 0.f; pb[i] = pre_bias ? pre_bias[cv * V + i] : 0.f; }
+    for (int i = 0; i < V; ++i) { s[i] = 0.0; q[i] = 0.0; }
+    if (lane_row < rif) {
         const size_t base = ((size_t)b * HW + row0) * stpr + scv;
         for (uint32_t r = lane_row; r < rows_per_block; r += rif) {
             float f[V];
             GnVec<DT>::load(src, base + (size_t)r * stpr, f);
 #pragma unroll
-            for (int i = 0; i < V; ++i) { const float v = f[i] + pb[i]; s[i] += v; q[i] = __builtin_fmaf(v, v, q[i]); }
+            for (int i = 0; i < V; ++i) { const double v = f[i]; s[i] += v; q[i] = __builtin_fma(v, v, q[i]); }
         }
+        if (pre_bias) {                                                    // sums of x + pb from those of x (exact in fp64; keeps pb out of the loop's registers)
+            const double n = (double)((rows_per_block - lane_row + rif - 1) / rif);
 #pragma unroll
-        for (int i = 0; i < V; ++i) { part_s[lane_row * C + cv * V + i] = s[i]; part_q[lane_row * C + cv * V + i] = q[i]; }
+            for (int i = 0; i < V; ++i) { const double pb = pre_bias[cv * V + i]; q[i] += pb * (2.0 * s[i] + n * pb); s[i] += n * pb; }
+        }
     }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < C; c += GN_TPB) {                   // fold the rows-in-flight, result in row 0
-        float s = 0.f, q = 0.f;
-        for (uint32_t r = 0; r < rif; ++r) { s += part_s[r * C + c]; q += part_q[r * C + c]; }
-        part_s[c] = s; part_q[c] = q;                                      // row 0 slot c is only read by this thread above
-    }
-    __syncthreads();
-    const uint32_t cpg = C / G;
-    for (uint32_t g = threadIdx.x; g < G; g += GN_TPB) {
-        double ds = 0.0, dq = 0.0;
-        for (uint32_t i = 0; i < cpg; ++i) { ds += (double)part_s[g * cpg + i]; dq += (double)part_q[g * cpg + i]; }
-        atomicAdd(&sums[((size_t)b * G + g) * 2 + 0], ds);
-        atomicAdd(&sums[((size_t)b * G + g) * 2 + 1], dq);
-    }
+    gn_fold_to_groups<V>(part, s, lane_row < rif, lane_row, cv, rif, C, G, sums + (size_t)b * G * 2);
+    gn_fold_to_groups<V>(part, q, lane_row < rif, lane_row, cv, rif, C, G, sums + (size_t)b * G * 2 + 1);
 }
 
 // RUNS (r03): the statistics arrive per (sample, RUN of 4 consecutive channels) instead of per group -- `sums` [B][C1 / 4][2] for x, `sums2`
@@ -261,13 +287,13 @@ __global__ __launch_bounds__(GN_TPB) void k_bias_residual(const void* __restrict
                                                            uint32_t HW, uint32_t C, uint32_t rows_per_block, void* __restrict__ y, double* __restrict__ sums,
                                                            uint32_t G) {
     constexpr int V = GnVec<DT>::V;
-    __shared__ float part_s[GN_TPB * V], part_q[GN_TPB * V];
+    __shared__ double part[GN_TPB * V];                                    // (fp64 sums from the first add, as k_gn_stats)
     const uint32_t tpr = C / V, rif = GN_TPB / tpr;
     const uint32_t lane_row = threadIdx.x / tpr, cv = threadIdx.x % tpr;
     const uint32_t b = blockIdx.y, row0 = blockIdx.x * rows_per_block;
-    float s[V], q[V];
+    double s[V], q[V];
 #pragma unroll
-    for (int i = 0; i < V; ++i) { s[i] = 0.f; q[i] = 0.f; }
+    for (int i = 0; i < V; ++i) { s[i] = 0.0; q[i] = 0.0; }
     if (lane_row < rif) {
         float bv[V];
 #pragma unroll
@@ -286,29 +312,13 @@ __global__ __launch_bounds__(GN_TPB) void k_bias_residual(const void* __restrict
             GnVec<DT>::store(y, base + (size_t)r * tpr, f);
             if (sums) {
 #pragma unroll
-                for (int i = 0; i < V; ++i) { const float v = GnVec<DT>::round(f[i]); s[i] += v; q[i] = __builtin_fmaf(v, v, q[i]); }   // what the next norm will read
+                for (int i = 0; i < V; ++i) { const double v = GnVec<DT>::round(f[i]); s[i] += v; q[i] = __builtin_fma(v, v, q[i]); }   // what the next norm will read
             }
         }
     }
     if (!sums) return;
-    if (lane_row < rif) {
-#pragma unroll
-        for (int i = 0; i < V; ++i) { part_s[lane_row * C + cv * V + i] = s[i]; part_q[lane_row * C + cv * V + i] = q[i]; }
-    }
-    __syncthreads();
-    for (uint32_t c = threadIdx.x; c < C; c += GN_TPB) {
-        float ss = 0.f, qq = 0.f;
-        for (uint32_t r = 0; r < rif; ++r) { ss += part_s[r * C + c]; qq += part_q[r * C + c]; }
-        part_s[c] = ss; part_q[c] = qq;
-    }
-    __syncthreads();
-    const uint32_t cpg = C / G;
-    for (uint32_t g = threadIdx.x; g < G; g += GN_TPB) {
-        double ds = 0.0, dq = 0.0;
-        for (uint32_t i = 0; i < cpg; ++i) { ds += (double)part_s[g * cpg + i]; dq += (double)part_q[g * cpg + i]; }
-        atomicAdd(&sums[((size_t)b * G + g) * 2 + 0], ds);
-        atomicAdd(&sums[((size_t)b * G + g) * 2 + 1], dq);
-    }
+    gn_fold_to_groups<V>(part, s, lane_row < rif, lane_row, cv, rif, C, G, sums + (size_t)b * G * 2);
+    gn_fold_to_groups<V>(part, q, lane_row < rif, lane_row, cv, rif, C, G, sums + (size_t)b * G * 2 + 1);
 }
 
 // ---- input gradient (frozen gamma / beta, time embedding independent of x): the arithmetic of gn_bwd_math.h over the same
