@@ -15,7 +15,8 @@
  *     lib/ops/raymarching/src/bindings.cpp:5-18   (signatures: raymarching.h:7-18)
  *     lib/ops/shencoder/src/bindings.cpp:5-8      (signatures: shencoder.h:9-12)
  * Part 2 is the fused fast path that sits behind TriPlaneDecoder.point_decode /
- * VolumeRenderer.forward / BaseNeRF.update_extra_state (same results, fewer HBM round trips).
+ * VolumeRenderer.forward / BaseNeRF.update_extra_state (same results, fewer HBM round trips), with the
+ * test-view scores and the total-variation regulariser of stage-1 fitting (TVLoss).
  *
  * All floating-point tensors are fp32 unless a dtype argument says otherwise (the reference's Python
  * wrappers force fp32 with custom_fwd(cast_inputs=torch.float32)).
@@ -297,6 +298,20 @@ int ssdnerf_quantize_u8(const float* x, uint64_t n, uint8_t* y, void* stream);
  * Window sums and vx, vy, vxy are formed in fp64.  No atomics, a fixed reduction order: bit-identical from run to run.
  * Null pointers, n == 0, h < 7 or w < 7 fail with SSDNERF_E_INVALID before any HIP call. */
 int ssdnerf_image_metrics(const float* a, const float* b, uint32_t n, uint32_t h, uint32_t w, float* mse, float* ssim, void* stream);
+
+/* Total-variation regulariser of stage-1 fitting (tv_loss, lib/models/losses/tv_loss.py, dims = [-2, -1], before mmgen's weighted_loss reduces it)
+ * over n contiguous fp32 slices x [n][h][w].  For element (i, j) of a slice: dy = x[i+1][j] - x[i][j] (0 on the last row), dx = x[i][j+1] - x[i][j]
+ * (0 on the last column), r = sqrt(dy^2 + dx^2).
+ *   forward:   slice_mean[k] = mean over the slice of r^power (fp32 [n]);
+ *   backward:  WRITES (does not accumulate) dx_out = g[k] / (h w) * d(sum of r^power over slice k) / dx for every element, g = the upstream
+ *              gradient of slice_mean (fp32 [n], read on the device).  An element collects its own term and those of its upper and left
+ *              neighbours; a term whose r == 0 contributes exactly 0 (PyTorch's norm backward): flat pixels get 0, never NaN.
+ * Per-element r^power and its derivative are fp32; the slice sums are fp64 in a fixed order, no atomics: bit-identical from run to run.
+ * No host synchronisation, no allocation, no workspace: safe inside a captured graph.
+ * Null pointers, n == 0, h == 0, w == 0, h * w > 2^30 and a power that is not a finite value >= 1 fail with SSDNERF_E_INVALID before any HIP
+ * call (below 1 the reference's gradient is NaN at every flat pixel). */
+int ssdnerf_tv_loss_forward(const float* x, uint32_t n, uint32_t h, uint32_t w, float power, float* slice_mean, void* stream);
+int ssdnerf_tv_loss_backward(const float* x, const float* g, uint32_t n, uint32_t h, uint32_t w, float power, float* dx_out, void* stream);
 
 /* ---- Part 3: denoising-UNet glue (lib/models/architecture/ddpm/modules.py:12-129, denoising.py:178-187) ------------------
  * Activations are channel-last: x, y are [B][HW][C] of dtype 0 = fp32, 1 = fp16, 2 = bf16.

@@ -31,7 +31,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("SSDNERF_LIB_DIR") or os.path.join(HERE, "lib")     # SSDNERF_LIB_DIR + SSDNERF_EXTRA_FLAGS: side builds for A/B runs
 LIB_PATH = os.path.join(LIB_DIR, "libssdnerf_hip.so")
-SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "ddim.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip"]
+SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "ddim.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip"]
 LLVM_BIN = os.environ.get("SSDNERF_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TRANS_USE_WAIT_STATES = int(os.environ.get("SSDNERF_TRANS_USE_WAIT_STATES", "1"))     # 1 = the toolchain's own distance: the r03 rule is off (r06)
 SWAP_MFMA_WAIT_STATES = int(os.environ.get("SSDNERF_SWAP_MFMA_WAIT_STATES", "0"))    # asm_postpass.SWAP_MFMA_WAIT_STATES (0 = rule off: the default since r06)
@@ -40,6 +40,9 @@ VALU_MFMA_WAIT_STATES = int(os.environ.get("SSDNERF_VALU_MFMA_WAIT_STATES", "0")
 HEADERS = ["common.h", "sh_basis.h", "decode_core.h", "decode_bwd_math.h", "gn_bwd_math.h", os.path.join("..", "..", "include", "ssdnerf_hip.h")]
 VALIDATED_HIP_VERSIONS = ("7.2.",)              # prefixes of `hipcc --version`'s "HIP version:" the post-pass + hazard analysis were validated on (r03 / r04)
 FLAGS = os.environ.get("SSDNERF_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-result"]
+# per-source additions: OCML's powf, SLP-vectorised, leaves a packed fp32 add whose halves overwrite each other's source (the post-pass cannot
+# split it in place); tv_loss.hip is elementwise, so plain fp32 instructions cost it nothing measurable
+SOURCE_FLAGS = {"tv_loss.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:
@@ -118,7 +121,8 @@ def _compile_with_postpass(src: str, obj: str, verbose: bool) -> dict:
     from .asm_postpass import closest_trans_use, pad_trans_use, verify_code_object
     stem = obj[:-2]
     dev_s, dev_o, dev_out, fatbin = stem + ".dev.s", stem + ".dev.o", stem + ".dev.out", stem + ".hipfb"
-    _run([_hipcc()] + FLAGS + ["-S", "--cuda-device-only", src, "-o", dev_s], verbose)
+    flags = FLAGS + SOURCE_FLAGS.get(os.path.basename(src), [])
+    _run([_hipcc()] + flags + ["-S", "--cuda-device-only", src, "-o", dev_s], verbose)
     with open(dev_s) as f:
         listing = f.read()
     from . import asm_postpass
@@ -154,7 +158,7 @@ def _compile_with_postpass(src: str, obj: str, verbose: bool) -> dict:
         stats["code_object_check"]["packed_cross_half"] = 0
     _run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "-type=o", "-bundle-align=4096",
           "-targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950", "-input=/dev/null", f"-input={dev_out}", f"-output={fatbin}"], verbose)
-    _run([_hipcc()] + FLAGS + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", fatbin, "-c", src, "-o", obj], verbose)
+    _run([_hipcc()] + flags + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", fatbin, "-c", src, "-o", obj], verbose)
     for tmp in (dev_s, dev_o, dev_out, fatbin):
         os.remove(tmp)
     return stats
@@ -177,7 +181,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         if postpass:
             report["sources"][src] = _compile_with_postpass(os.path.join(CSRC, src), obj, verbose)
         else:
-            _run([_hipcc()] + FLAGS + ["-c", os.path.join(CSRC, src), "-o", obj], verbose)
+            _run([_hipcc()] + FLAGS + SOURCE_FLAGS.get(src, []) + ["-c", os.path.join(CSRC, src), "-o", obj], verbose)
         objs.append(obj)
     _run([_hipcc(), "--offload-arch=gfx950", "-shared", "-o", LIB_PATH] + objs, verbose)
     with open(os.path.join(LIB_DIR, "postpass_report.json"), "w") as f:

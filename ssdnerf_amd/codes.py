@@ -101,6 +101,32 @@ class RegLoss(nn.Module):
         return (mag if self.power == 1 else mag ** self.power).mean() * self.loss_weight
 
 
+@MODULES.register_module()
+class TVLoss(nn.Module):
+    """``loss_weight * mean(tv_slice_means(x, power))``: the reference's total-variation loss (lib/models/losses/tv_loss.py) over the two trailing
+    dimensions of the scene codes, reduced as mmgen's ``weighted_loss`` does with its default ``reduction='mean'``.  Forward and backward are
+    HIP kernels (tv_loss.py).  ``dims`` must name the two trailing dimensions (``[-2, -1]``, ``(-1, -2)``, ``[3, 4]`` of a 5-dim code ...);
+    ``weight`` / ``avg_factor`` exist for the reference's signature, and a value other than None raises."""
+
+    def __init__(self, dims=(-2, -1), power=1, loss_weight=1.0):
+        super().__init__()
+        self.dims, self.power, self.loss_weight = list(dims), power, loss_weight
+        if not power >= 1:
+            raise ValueError(f"TVLoss: power={power!r}: powers below 1 have no finite gradient where the code is flat")
+
+    def _check_dims(self, ndim):
+        trailing = {ndim - 2, ndim - 1}
+        if len(self.dims) != 2 or {d % ndim if -ndim <= d < ndim else None for d in self.dims} != trailing:
+            raise ValueError(f"TVLoss: dims={self.dims} do not name the two trailing dimensions of a {ndim}-dim tensor")
+
+    def forward(self, tensor, weight=None, avg_factor=None):
+        if weight is not None or avg_factor is not None:
+            raise NotImplementedError("TVLoss: weight / avg_factor are not supported (no config passes them)")
+        self._check_dims(tensor.dim())
+        from .tv_loss import tv_slice_means
+        return tv_slice_means(tensor, self.power).mean() * self.loss_weight
+
+
 class _ConfigOnly(nn.Module):
     """Config entries that only the (out-of-scope) training loop executes: constructible, so that the reference's configs build unchanged."""
 
@@ -112,8 +138,7 @@ class _ConfigOnly(nn.Module):
         raise NotImplementedError(f"{type(self).__name__} belongs to the training loop, which is outside the hot path")
 
 
-for _name in ("TVLoss", "L1LossMod"):
-    MODULES.register_module(name=_name, module=type(_name, (_ConfigOnly,), {}))
+MODULES.register_module(name="L1LossMod", module=type("L1LossMod", (_ConfigOnly,), {}))
 
 
 # ---------------------------------------------------------------------------------------------- small utilities

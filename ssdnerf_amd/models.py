@@ -26,7 +26,7 @@ import torch.nn as nn
 
 from . import nerf
 from .codes import attr_path_get, attr_path_set, frozen
-from .codes import IdentityCode, MSELoss, NormalizedTanhCode, RegLoss, TanhCode  # noqa: F401  (registered here for config builds)
+from .codes import IdentityCode, MSELoss, NormalizedTanhCode, RegLoss, TanhCode, TVLoss  # noqa: F401  (registered here for config builds)
 from .density import get_density as _get_density, update_density_grid
 from .fitting import CodeFitter, Conditioning, GuidanceObjective, RayBatcher
 from .metrics import image_metrics
@@ -56,9 +56,10 @@ class BaseNeRF(nn.Module):
         self.train_cfg, self.test_cfg = dict(train_cfg or {}), dict(test_cfg or {})
         self.update_extra_interval = update_extra_interval
         self.init_scale, self.mean_ema_momentum, self.mean_scale = init_scale, mean_ema_momentum, mean_scale
-        self.init_code = None
-        if init_from_mean:
+        if init_from_mean:              # the running mean code of the stage-1 configs: a buffer (a plain attribute first would make it a KeyError)
             self.register_buffer("init_code", torch.zeros(self.code_size))
+        else:
+            self.init_code = None
         if pretrained is not None and os.path.isfile(pretrained):
             ckpt = torch.load(pretrained, map_location="cpu")
             self.load_state_dict(ckpt.get("state_dict", ckpt), strict=False)
@@ -228,6 +229,50 @@ class BaseNeRF(nn.Module):
 
     def train_step(self, data, optimizer, running_status=None):
         raise NotImplementedError("BaseNeRF has no training step of its own; MultiSceneNeRF / DiffusionNeRF do")
+
+    # ---- evaluation ------------------------------------------------------------------------------------------------------------------------------
+    def _eval_test_views(self, data, decoder, code, density_bitfield):
+        """``test_poses`` rendered and quantised to k/255, and scored -> (log_vars, pred_imgs (S, V, 3, h, w) or None, extras).  As
+        ``eval_and_viz`` (base_nerf.py:535-558): with ``test_imgs`` (S, V, h, w, 3) in the batch and ``test_cfg['skip_eval']`` unset, the views are
+        rendered at the ground truth's size and scored against it -- ``log_vars`` holds ``test_psnr`` / ``test_ssim``, the means over all views, and
+        the extras ``test_metrics``, the per-view values as (S, V) device tensors (metrics.image_metrics).  LPIPS is not computed."""
+        pred, log_vars, extra = None, dict(), dict()
+        if "test_poses" in data:
+            evaluate = "test_imgs" in data and not self.test_cfg.get("skip_eval", False)
+            h, w = data["test_imgs"].shape[2:4] if evaluate else self.test_cfg.get("img_size", (128, 128))
+            image, _ = self.render(decoder, code, density_bitfield, h, w, data["test_intrinsics"], data["test_poses"], cfg=self.test_cfg)
+            image = torch.round(image.clamp(0, 1) * 255) / 255
+            if evaluate:
+                psnr, ssim = image_metrics(image, data["test_imgs"].to(image.device, torch.float32))
+                log_vars = dict(test_psnr=float(psnr.mean()), test_ssim=float(ssim.mean()))
+                extra["test_metrics"] = dict(psnr=psnr, ssim=ssim)
+            pred = image.permute(0, 1, 4, 2, 3)
+        return log_vars, pred, extra
+
+    def val_step(self, data, march_noises=None, density_jitters=None, **kwargs):
+        """Reconstruction by optimisation, then evaluation (base_nerf.py:622-673): the batch's scene files (``data['code']``), or codes fitted to
+        ``cond_imgs`` by ``test_cfg['n_inverse_steps']`` iterations of ``inverse_code`` (the test_cfg's optimizer and LR schedule; ``march_noises`` /
+        ``density_jitters``: injected draws, consumed in order); ``test_poses`` rendered and scored as ``_eval_test_views``.  ``log_vars`` adds
+        ``train_psnr`` (the last inversion iteration's rendered rays against their targets; only when inversion ran) and ``code_rms``; with
+        ``test_cfg['save_dir']`` the scenes are written by ``save_scene``.  Returns the keys of ``DiffusionNeRF.val_step``."""
+        decoder = self._modules_for_eval()
+        rgb = target = None
+        if "code" in data:
+            code, grid, bits = self.load_scene(data, load_density=True)
+        else:
+            cond = Conditioning.from_batch(data, self.test_cfg.get("dt_gamma_scale", 0.0))
+            with torch.enable_grad():
+                code, grid, bits, _, _, rgb, target = self.inverse_code(decoder, cond.images, cond.rays_o, cond.rays_d, dt_gamma=cond.dt_gamma,
+                                                                        cfg=self.test_cfg, march_noises=march_noises, density_jitters=density_jitters)
+        with torch.no_grad():
+            log_vars, pred, extra = self._eval_test_views(data, decoder, code, bits)
+            if rgb is not None:
+                log_vars.update(train_psnr=float(nerf.eval_psnr(rgb.detach(), target).mean()))
+            log_vars.update(code_rms=float(code.square().flatten(1).mean().sqrt().mean()))
+        save_dir = self.test_cfg.get("save_dir", None)
+        if save_dir is not None:
+            self.save_scene(save_dir, code, grid, bits, data["scene_name"])
+        return dict(log_vars=log_vars, num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits, **extra)
 
     @staticmethod
     def _log_fit(log_vars, rgb, target, code):
@@ -631,21 +676,9 @@ class DiffusionNeRF(MultiSceneNeRF):
         raise AttributeError(f"cond_mode={mode!r}")
 
     def val_step(self, data, **kwargs):
-        """Scene codes for the batch, and its ``test_poses`` rendered and quantised to k/255 (``pred_imgs``, (S, V, 3, h, w)).  As ``eval_and_viz``
-        (base_nerf.py:535-558): with ``test_imgs`` (S, V, h, w, 3) in the batch and ``test_cfg['skip_eval']`` unset, the views are rendered at the
-        ground truth's size and scored against it -- ``log_vars`` holds ``test_psnr`` / ``test_ssim``, the means over all views, and ``test_metrics``
-        the per-view values as (S, V) device tensors (metrics.image_metrics).  LPIPS is not computed."""
+        """Scene codes for the batch (``_scene_from``), and its ``test_poses`` rendered, quantised to k/255 (``pred_imgs``, (S, V, 3, h, w)) and
+        scored against ``test_imgs`` as ``BaseNeRF._eval_test_views`` does."""
         with torch.no_grad():
             code, grid, bits = self._scene_from(data, kwargs)
-            pred, log_vars, extra = None, dict(), dict()
-            if "test_poses" in data:
-                evaluate = "test_imgs" in data and not self.test_cfg.get("skip_eval", False)
-                h, w = data["test_imgs"].shape[2:4] if evaluate else self.test_cfg.get("img_size", (128, 128))
-                image, _ = self.render(self._modules_for_eval(), code, bits, h, w, data["test_intrinsics"], data["test_poses"], cfg=self.test_cfg)
-                image = torch.round(image.clamp(0, 1) * 255) / 255
-                if evaluate:
-                    psnr, ssim = image_metrics(image, data["test_imgs"].to(image.device, torch.float32))
-                    log_vars = dict(test_psnr=float(psnr.mean()), test_ssim=float(ssim.mean()))
-                    extra["test_metrics"] = dict(psnr=psnr, ssim=ssim)
-                pred = image.permute(0, 1, 4, 2, 3)
+            log_vars, pred, extra = self._eval_test_views(data, self._modules_for_eval(), code, bits)
         return dict(log_vars=log_vars, num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits, **extra)
