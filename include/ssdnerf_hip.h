@@ -16,7 +16,8 @@
  *     lib/ops/shencoder/src/bindings.cpp:5-8      (signatures: shencoder.h:9-12)
  * Part 2 is the fused fast path that sits behind TriPlaneDecoder.point_decode /
  * VolumeRenderer.forward / BaseNeRF.update_extra_state (same results, fewer HBM round trips), with the
- * test-view scores and the total-variation regulariser of stage-1 fitting (TVLoss).
+ * test-view scores, the total-variation regulariser of stage-1 fitting (TVLoss), and mesh export: marching cubes and the
+ * per-vertex normals and colours that go into the mesh file.
  *
  * All floating-point tensors are fp32 unless a dtype argument says otherwise (the reference's Python
  * wrappers force fp32 with custom_fwd(cast_inputs=torch.float32)).
@@ -465,6 +466,17 @@ int ssdnerf_marching_cubes_count(const float* volume, uint32_t nx, uint32_t ny, 
 int ssdnerf_marching_cubes_emit(const float* volume, uint32_t nx, uint32_t ny, uint32_t nz, float iso, const uint8_t* tri_count,
                                 const int8_t* tri_edges, const int32_t* tri_offsets, const int32_t* vert_offsets, const uint8_t* point_mask,
                                 float* vertices, int32_t* triangles, void* stream);
+/* Surface attributes at the V vertices of such a mesh, one lane per vertex (csrc/mesh_attr.hip).  verts_idx fp32 [V][3] in the
+ * index coordinates _emit writes; b_min / scale: HOST arrays of three floats, the lattice map world = fma(v, scale, b_min) with
+ * scale = (b_max - b_min) / (res - 1) (the only host pointers of this ABI: six floats, passed to the kernel by value).  planes / mlp_params /
+ * sigmoid_saturation as in ssdnerf_point_decode.  Outputs: xyz fp32 [V][3] world positions; sigma fp32 [V]; grad_sigma fp32 [V][3] = d sigma / d xyz
+ * (nullable), exactly 0 along an axis on which the gather clipped (grid_sample's border rule); normals fp32 [V][3] = -grad / |grad|, pointing from
+ * high density to low like the triangle winding, 0 where the gradient is 0; colors fp32 [V][3] = the decoder's rgb at the vertex for the view
+ * direction -normal (seen head-on from outside; (0, 0, 1) where the normal is 0), in the decoder's range [-sat, 1 + sat]; colors_u8 uint8 [V][3] =
+ * ssdnerf_quantize_u8 of colors (nullable).  No atomics: two calls return the same bits.  V == 0 is a no-op that returns 0. */
+int ssdnerf_mesh_vertex_attributes(const void* planes, int planes_dtype, uint32_t Hp, uint32_t Wp, const float* mlp_params, const float* verts_idx,
+                                   uint32_t V, const float* b_min, const float* scale, float sigmoid_saturation, float* xyz, float* sigma,
+                                   float* grad_sigma, float* normals, float* colors, uint8_t* colors_u8, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,7 +13,11 @@ case closes, <= 5 triangles, complementary cases use the same edges) and the pur
 oriented manifold, Euler characteristic, area, enclosed volume); the GPU tests check the kernels against this walker.
 
 Conventions (PyMCubes'): ``volume[x, y, z]``, vertices in index coordinates (float), a corner is INSIDE when its value is greater than the
-iso-value, triangles wind counter-clockwise seen from the outside (normals point from high density to low)."""
+iso-value, triangles wind counter-clockwise seen from the outside (normals point from high density to low).
+
+Around it, the export: ``vertex_attributes`` -- normals and colours at the vertices from the radiance field itself, one HIP
+kernel (csrc/mesh_attr.hip) -- and the file formats, ``write_stl`` / ``write_ply`` with ``read_stl`` / ``read_ply`` for exactly those layouts (the
+reference exports through ``trimesh``, which is not available here)."""
 from __future__ import annotations
 
 from functools import lru_cache
@@ -214,3 +218,174 @@ def mesh_stats(vertices: np.ndarray, triangles: np.ndarray) -> dict:
     return dict(directed_edges_unique=bool((cf == 1).all()), closed_and_oriented=bool((cf == 1).all() and np.array_equal(uf, np.unique(rev))),
                 euler=n - len(uf) // 2 + len(tri), area=float(0.5 * np.linalg.norm(cross, axis=1).sum()),
                 volume=float((p[:, 0] * cross).sum() / 6.0), degenerate=int((np.linalg.norm(cross, axis=1) == 0).sum()))
+
+
+# ---------------------------------------------------------------------------------------------- surface attributes and mesh files
+def lattice_map(b_min, b_max, resolution: int) -> Tuple[np.ndarray, np.ndarray]:
+    """(b_min, scale) as float32 arrays: index coordinates -> world is ``fma(v, scale, b_min)``, scale = (b_max - b_min) / (resolution - 1) formed in
+    float64 from the float32 box corners and rounded once"""
+    lo = np.asarray(b_min, dtype=np.float32).reshape(3)
+    hi = np.asarray(b_max, dtype=np.float32).reshape(3)
+    return lo, ((hi.astype(np.float64) - lo.astype(np.float64)) / (resolution - 1.0)).astype(np.float32)
+
+
+def vertex_attributes(decoder, code_single, verts_idx, b_min, b_max, resolution: int, want_grad: bool = False) -> dict:
+    """Per-vertex surface attributes of one scene from the radiance field itself, one HIP kernel (csrc/mesh_attr.hip), everything on the device.
+
+    ``verts_idx`` (V, 3) float32: vertices in the index coordinates ``marching_cubes`` returns, on the ``resolution``^3 lattice spanning
+    [``b_min``, ``b_max``].  Returns ``xyz`` (V, 3) world positions (``fma(v, scale, b_min)``), ``sigma`` (V), ``normals`` (V, 3): minus the normalised
+    density gradient -- it points from high density to low, the side the triangles of ``marching_cubes`` face -- and 0 where the gradient is 0,
+    ``colors`` (V, 3): the decoder's rgb at the vertex for the view direction ``-normal``, i.e. the surface seen head-on from outside (direction
+    (0, 0, 1) where the normal is 0), in the decoder's range, ``colors_u8`` (V, 3) uint8 = round(clamp(colors, 0, 1) * 255), and with ``want_grad``
+    ``grad_sigma`` (V, 3) = d sigma / d xyz (exactly 0 along an axis on which ``grid_sample``'s border rule clipped the coordinate).
+
+    Only the decoder the fused kernels support (``TriPlaneDecoder.fused_supported``); any other raises ``NotImplementedError``: there is no
+    fallback path."""
+    import torch
+
+    from . import _cabi as C
+    from .decoders import pack_triplanes
+    code = code_single[None] if code_single.dim() == 4 else code_single
+    if not (hasattr(decoder, "fused_supported") and decoder.fused_supported(code)):
+        raise NotImplementedError("vertex_attributes: only the decoder of the fused kernels (18 -> 64 -> {sigma, rgb}, SiLU, TruncExp, SH degree 4, no flip_z, "
+                                  "6-channel planes on the GPU) is supported")
+    assert code.size(0) == 1, "vertex_attributes: one scene"
+    dev = code.device
+    verts = verts_idx.detach().to(dev, torch.float32).reshape(-1, 3).contiguous()
+    n = int(verts.size(0))
+    out = dict(xyz=torch.empty(n, 3, dtype=torch.float32, device=dev), sigma=torch.empty(n, dtype=torch.float32, device=dev),
+               normals=torch.empty(n, 3, dtype=torch.float32, device=dev), colors=torch.empty(n, 3, dtype=torch.float32, device=dev),
+               colors_u8=torch.empty(n, 3, dtype=torch.uint8, device=dev))
+    if want_grad:
+        out["grad_sigma"] = torch.empty(n, 3, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    planes = pack_triplanes(code.detach(), decoder.plane_dtype)
+    lo, scale = lattice_map(b_min, b_max, resolution)
+    f3 = C.ctypes.c_float * 3
+    _, _, hp, wp, _ = planes.shape
+    C.check(C.lib().ssdnerf_mesh_vertex_attributes(C.ptr(planes), C.dtype_code(planes), C.u32(hp), C.u32(wp), C.ptr(decoder.packed_params()), C.ptr(verts),
+                                                   C.u32(n), f3(*lo.tolist()), f3(*scale.tolist()), C.f32(decoder.sigmoid_saturation), C.ptr(out["xyz"]),
+                                                   C.ptr(out["sigma"]), C.ptr(out.get("grad_sigma")), C.ptr(out["normals"]), C.ptr(out["colors"]),
+                                                   C.ptr(out["colors_u8"]), C.stream()), "mesh_vertex_attributes")
+    return out
+
+
+_STL_RECORD = np.dtype([("normal", "<f4", (3,)), ("vertices", "<f4", (3, 3)), ("attr", "<u2")])
+assert _STL_RECORD.itemsize == 50
+
+
+def write_stl(path, vertices, triangles) -> None:
+    """Binary STL: 80-byte header, uint32 triangle count, one 50-byte record per triangle (unit face normal from the winding, the three vertices as
+    float32, uint16 0).  A degenerate triangle gets the normal 0."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int64).reshape(-1, 3)
+    rec = np.zeros(len(t), dtype=_STL_RECORD)
+    p = v[t]                                                                             # (T, 3, 3)
+    rec["vertices"] = p
+    rec["normal"] = _face_normals(p)
+    with open(path, "wb") as f:
+        f.write(b"ssdnerf_amd binary STL".ljust(80, b" "))
+        f.write(np.uint32(len(t)).astype("<u4").tobytes())
+        f.write(rec.tobytes())
+
+
+def _face_normals(p: np.ndarray) -> np.ndarray:
+    """unit normals (float32) of triangles p (T, 3, 3) from their winding, computed in float64; 0 for a degenerate triangle"""
+    p = p.astype(np.float64)
+    c = np.cross(p[:, 1] - p[:, 0], p[:, 2] - p[:, 0])
+    n = np.linalg.norm(c, axis=1, keepdims=True)
+    return np.where(n > 0, c / np.where(n > 0, n, 1.0), 0.0).astype(np.float32)
+
+
+def read_stl(path) -> Tuple[np.ndarray, np.ndarray]:
+    """``write_stl``'s layout back: (face normals (T, 3) float32, corners (T, 3, 3) float32).  STL stores no indices: every triangle carries its own
+    three vertices."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 84:
+        raise ValueError(f"{path}: shorter than a binary STL header")
+    n = int(np.frombuffer(raw, "<u4", 1, 80)[0])
+    if len(raw) != 84 + 50 * n:
+        raise ValueError(f"{path}: {len(raw)} bytes, but the header announces {n} triangles ({84 + 50 * n} bytes)")
+    rec = np.frombuffer(raw, _STL_RECORD, n, 84)
+    return rec["normal"].copy(), rec["vertices"].copy()
+
+
+def _ply_vertex_dtype(normals: bool, colors: bool) -> np.dtype:
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    if normals:
+        fields += [("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4")]
+    if colors:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+    return np.dtype(fields)
+
+
+_PLY_FACE = np.dtype([("n", "u1"), ("idx", "<i4", (3,))])
+_PLY_TYPES = {"<f4": "float", "|u1": "uchar"}
+
+
+def ply_header(n_vertices: int, n_faces: int, normals: bool, colors: bool) -> str:
+    lines = ["ply", "format binary_little_endian 1.0", "comment ssdnerf_amd", f"element vertex {n_vertices}"]
+    lines += [f"property {_PLY_TYPES[_ply_vertex_dtype(normals, colors)[name].str]} {name}" for name in _ply_vertex_dtype(normals, colors).names]
+    lines += [f"element face {n_faces}", "property list uchar int vertex_indices", "end_header"]
+    return "\n".join(lines) + "\n"
+
+
+def write_ply(path, vertices, triangles, normals=None, colors=None) -> None:
+    """Binary little-endian PLY: vertex ``x y z`` [``nx ny nz``] float [``red green blue`` uchar], faces as ``list uchar int vertex_indices``.
+    ``colors``: (V, 3) uint8."""
+    v = np.asarray(vertices, dtype=np.float32).reshape(-1, 3)
+    t = np.asarray(triangles, dtype=np.int32).reshape(-1, 3)
+    vd = _ply_vertex_dtype(normals is not None, colors is not None)
+    rec = np.zeros(len(v), dtype=vd)
+    cols = [v]
+    if normals is not None:
+        cols.append(np.asarray(normals, dtype=np.float32).reshape(len(v), 3))
+    for a, name in zip(np.concatenate(cols, axis=1).T, vd.names):
+        rec[name] = a
+    if colors is not None:
+        c = np.asarray(colors)
+        if c.dtype != np.uint8:
+            raise TypeError("write_ply: colors must be uint8 (V, 3)")
+        for a, name in zip(c.reshape(len(v), 3).T, ("red", "green", "blue")):
+            rec[name] = a
+    faces = np.zeros(len(t), dtype=_PLY_FACE)
+    faces["n"] = 3
+    faces["idx"] = t
+    with open(path, "wb") as f:
+        f.write(ply_header(len(v), len(t), normals is not None, colors is not None).encode("ascii"))
+        f.write(rec.tobytes())
+        f.write(faces.tobytes())
+
+
+def read_ply(path) -> dict:
+    """``write_ply``'s layouts back: dict(vertices (V, 3) float32, triangles (T, 3) int32, normals (V, 3) float32 or None, colors (V, 3) uint8 or
+    None).  Any other PLY (ascii, other properties, polygons) is a ``ValueError``."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.find(b"end_header\n")
+    if end < 0:
+        raise ValueError(f"{path}: no PLY header")
+    head = raw[:end + len(b"end_header\n")].decode("ascii")
+    lines = head.split("\n")
+    try:
+        nv = int(lines[3].split()[2])
+        names = [l.split()[2] for l in lines[4:] if l.startswith("property") and not l.startswith("property list")]
+        nf = int(next(l for l in lines if l.startswith("element face")).split()[2])
+    except (IndexError, ValueError, StopIteration):
+        raise ValueError(f"{path}: not a PLY header of write_ply") from None
+    has_n, has_c = "nx" in names, "red" in names
+    if head != ply_header(nv, nf, has_n, has_c):
+        raise ValueError(f"{path}: not one of write_ply's layouts")
+    vd = _ply_vertex_dtype(has_n, has_c)
+    body = len(head)
+    if len(raw) != body + nv * vd.itemsize + nf * _PLY_FACE.itemsize:
+        raise ValueError(f"{path}: size does not match the header's counts")
+    rec = np.frombuffer(raw, vd, nv, body)
+    faces = np.frombuffer(raw, _PLY_FACE, nf, body + nv * vd.itemsize)
+    if nf and not (faces["n"] == 3).all():
+        raise ValueError(f"{path}: a face that is not a triangle")
+    stack = lambda keys, dt: np.stack([rec[k] for k in keys], axis=1).astype(dt)
+    return dict(vertices=stack(("x", "y", "z"), np.float32), triangles=faces["idx"].astype(np.int32).reshape(-1, 3),
+                normals=stack(("nx", "ny", "nz"), np.float32) if has_n else None, colors=stack(("red", "green", "blue"), np.uint8) if has_c else None)

@@ -104,6 +104,38 @@ class BaseNeRF(nn.Module):
             param = dict(code=code.data[i].cpu(), density_grid=density_grid.data[i].cpu(), density_bitfield=density_bitfield.data[i].cpu())
             torch.save(dict(scene_name=name, param=param), os.path.join(save_dir, name) + ".pth")
 
+    @staticmethod
+    def save_mesh(save_dir, decoder, code, scene_name, mesh_resolution, mesh_threshold, mesh_format="stl"):
+        """One mesh file per scene under ``save_dir`` (base_nerf.py:172-182, plus the format): ``'stl'`` writes ``<scene_name>.stl``, the bare
+        geometry the reference exports; ``'ply'`` writes ``<scene_name>.ply`` with the field's normals and colours at the vertices
+        (``nerf.extract_surface``).  A scene with nothing above the threshold gets a valid file with zero triangles, and a warning."""
+        from . import mesh as M
+        if mesh_format not in ("stl", "ply"):
+            raise ValueError(f"mesh_format={mesh_format!r}: 'stl' or 'ply'")
+        os.makedirs(save_dir, exist_ok=True)
+        for code_single, name in zip(code, scene_name):
+            surf = nerf.extract_surface(decoder, code_single.detach(), resolution=mesh_resolution, threshold=mesh_threshold)
+            if len(surf.triangles) == 0:
+                warnings.warn(f"save_mesh: scene {name!r} has no density above {mesh_threshold}; writing an empty mesh")
+            path = os.path.join(save_dir, name) + "." + mesh_format
+            if mesh_format == "stl":
+                M.write_stl(path, surf.vertices, surf.triangles)
+            else:
+                M.write_ply(path, surf.vertices, surf.triangles, normals=surf.normals, colors=surf.colors_u8)
+
+    def _save_outputs(self, data, decoder, code, density_grid, density_bitfield):
+        """the tail of both ``val_step``s (diffusion_nerf.py:453-461): with ``test_cfg['save_dir']`` the scene files, and nested under it, with
+        ``test_cfg['save_mesh']``, the meshes (``mesh_resolution`` 256, ``mesh_threshold`` 10, ``mesh_format`` 'stl')"""
+        save_dir = self.test_cfg.get("save_dir", None)
+        if save_dir is None:
+            return
+        if "scene_name" not in data:
+            raise KeyError("val_step: test_cfg['save_dir'] is set, so the batch needs data['scene_name'] (one file name per scene)")
+        self.save_scene(save_dir, code, density_grid, density_bitfield, data["scene_name"])
+        if self.test_cfg.get("save_mesh", False):
+            self.save_mesh(save_dir, decoder, code, data["scene_name"], self.test_cfg.get("mesh_resolution", 256),
+                           self.test_cfg.get("mesh_threshold", 10), self.test_cfg.get("mesh_format", "stl"))
+
     # ---- fresh per-scene state ------------------------------------------------------------------------------------------------------------
     def get_init_code_(self, num_scenes, device=None):
         """A pre-activation code leaf, (code_size) or (S, code_size): uniform in +-init_scale, or the inverse-activated running mean code."""
@@ -254,7 +286,8 @@ class BaseNeRF(nn.Module):
         ``cond_imgs`` by ``test_cfg['n_inverse_steps']`` iterations of ``inverse_code`` (the test_cfg's optimizer and LR schedule; ``march_noises`` /
         ``density_jitters``: injected draws, consumed in order); ``test_poses`` rendered and scored as ``_eval_test_views``.  ``log_vars`` adds
         ``train_psnr`` (the last inversion iteration's rendered rays against their targets; only when inversion ran) and ``code_rms``; with
-        ``test_cfg['save_dir']`` the scenes are written by ``save_scene``.  Returns the keys of ``DiffusionNeRF.val_step``."""
+        ``test_cfg['save_dir']`` the scenes are written by ``save_scene`` and, with ``test_cfg['save_mesh']``, their meshes by ``save_mesh``
+        (``_save_outputs``).  Returns the keys of ``DiffusionNeRF.val_step``."""
         decoder = self._modules_for_eval()
         rgb = target = None
         if "code" in data:
@@ -269,9 +302,7 @@ class BaseNeRF(nn.Module):
             if rgb is not None:
                 log_vars.update(train_psnr=float(nerf.eval_psnr(rgb.detach(), target).mean()))
             log_vars.update(code_rms=float(code.square().flatten(1).mean().sqrt().mean()))
-        save_dir = self.test_cfg.get("save_dir", None)
-        if save_dir is not None:
-            self.save_scene(save_dir, code, grid, bits, data["scene_name"])
+        self._save_outputs(data, decoder, code, grid, bits)
         return dict(log_vars=log_vars, num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits, **extra)
 
     @staticmethod
@@ -677,8 +708,10 @@ class DiffusionNeRF(MultiSceneNeRF):
 
     def val_step(self, data, **kwargs):
         """Scene codes for the batch (``_scene_from``), and its ``test_poses`` rendered, quantised to k/255 (``pred_imgs``, (S, V, 3, h, w)) and
-        scored against ``test_imgs`` as ``BaseNeRF._eval_test_views`` does."""
+        scored against ``test_imgs`` as ``BaseNeRF._eval_test_views`` does.  With ``test_cfg['save_dir']`` the scenes are then written by
+        ``save_scene`` and, with ``test_cfg['save_mesh']``, their meshes by ``save_mesh`` (``_save_outputs``)."""
         with torch.no_grad():
             code, grid, bits = self._scene_from(data, kwargs)
             log_vars, pred, extra = self._eval_test_views(data, self._modules_for_eval(), code, bits)
+            self._save_outputs(data, self._modules_for_eval(), code, grid, bits)
         return dict(log_vars=log_vars, num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits, **extra)

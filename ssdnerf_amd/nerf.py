@@ -4,6 +4,7 @@ lib/core/utils/nerf_utils.py:17-61 ``get_cam_rays``), host orchestration in Pyth
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -260,3 +261,32 @@ def extract_geometry(decoder: TriPlaneDecoder, code_single: torch.Tensor, resolu
     b_min = (decoder.aabb[:3] - 0.1).cpu().numpy()
     b_max = (decoder.aabb[3:] + 0.1).cpu().numpy()
     return vertices / (resolution - 1.0) * (b_max - b_min)[None, :] + b_min[None, :], triangles
+
+
+@dataclass
+class Surface:
+    """An extracted iso-surface as numpy arrays: ``vertices`` (V, 3) float32 in world coordinates, ``triangles`` (T, 3) int32 (counter-clockwise seen
+    from outside), and -- with ``attributes`` -- ``normals`` (V, 3) float32 (unit, outward), ``colors_u8`` (V, 3) uint8, ``colors`` (V, 3) float32 in
+    the decoder's range (``mesh.vertex_attributes``); ``None`` without."""
+    vertices: "np.ndarray"
+    triangles: "np.ndarray"
+    normals: Optional["np.ndarray"] = None
+    colors_u8: Optional["np.ndarray"] = None
+    colors: Optional["np.ndarray"] = None
+
+
+@torch.no_grad()
+def extract_surface(decoder: TriPlaneDecoder, code_single: torch.Tensor, resolution: int = 256, threshold: float = 10, attributes: bool = True) -> Surface:
+    """``extract_geometry``'s surface (same density volume, same marching cubes, same lattice map in fp32) together with what the field knows at every
+    vertex: the exact normal (the density gradient) and a colour.  The index-coordinate vertices go from the marching-cubes kernels to the attribute
+    kernel (csrc/mesh_attr.hip) without leaving the device; one copy to the host at the end.  Without ``attributes`` the same kernel still maps the
+    vertices to world coordinates and the other fields stay ``None``."""
+    from . import mesh as M
+    u = extract_density_volume(decoder, code_single, resolution)
+    v_idx, tris = M.marching_cubes(u, threshold)
+    aabb = decoder.aabb.detach().cpu()
+    att = M.vertex_attributes(decoder, code_single, v_idx, (aabb[:3] - 0.1).numpy(), (aabb[3:] + 0.1).numpy(), resolution)
+    host = lambda t: t.cpu().numpy()
+    if not attributes:
+        return Surface(host(att["xyz"]), host(tris))
+    return Surface(host(att["xyz"]), host(tris), host(att["normals"]), host(att["colors_u8"]), host(att["colors"]))
