@@ -478,6 +478,30 @@ int ssdnerf_mesh_vertex_attributes(const void* planes, int planes_dtype, uint32_
                                    uint32_t V, const float* b_min, const float* scale, float sigmoid_saturation, float* xyz, float* sigma,
                                    float* grad_sigma, float* normals, float* colors, uint8_t* colors_u8, void* stream);
 
+/* ---- LPIPS v0.1, net = 'vgg': everything around the trunk's convolutions (csrc/lpips.hip) --------------------------------------
+ * The thirteen 3 x 3 convolutions are ssdnerf_conv2d_nhwc_f32x2 / _presplit, bias included; these entries are the single passes between them.  All tensors
+ * fp32 channel-last, 16-byte aligned, below 2^31 bytes; no atomics, so two calls return the same bits.  ReLU and max-pool keep a NaN, as torch.relu and
+ * torch's max_pool2d do (-0 becomes +0), so a NaN anywhere in an image makes that pair's acc NaN and no other's.
+ *
+ * _lpips_input: pred, target fp32 [n][h][w][3] in [0, 1] -> out [2n][h][w][8], predictions first and targets behind:
+ *   out[..][c] = ((2 img - 1) - shift_c) / scale_c, shift = (-.030, -.088, -.188), scale = (.458, .448, .450) as the nearest fp32 values, three fp32
+ *   roundings in that order; channels 3 .. 7 are exactly 0 (the first convolution runs with Cin = 8, its weights zero-padded to match). */
+int ssdnerf_lpips_input(const float* pred, const float* target, uint32_t n, uint32_t h, uint32_t w, float* out, void* stream);
+/* y = max(x, 0) of x [N][H][W][C] (C % 8 == 0), with pool != 0 followed by the 2 x 2 / stride 2 max-pool in floor mode -> [N][H / 2][W / 2][C] (an odd last
+ * row or column is dropped).  split_out != 0 (C % 32 == 0): y is written in the PRE-SPLIT layout ssdnerf_conv2d_nhwc_f32x2_presplit takes (the bytes of
+ * ssdnerf_split_f32_nhwc of the plain output); ask for it only when ssdnerf_conv2d_nhwc_f32x2_presplit_supported accepts the layer that reads y. */
+int ssdnerf_relu_pool_nhwc(const float* x, uint32_t N, uint32_t H, uint32_t W, uint32_t C, int pool, int split_out, void* y, void* stream);
+/* A tap.  x [2n][H][W][C]: the raw output (bias in, no ReLU) of trunk convolution 2 / 4 / 7 / 10 / 13 for n predictions and, behind them, their n targets;
+ * C in {64, 128, 256, 512}; lin_w fp32 [C], the tap's 1 x 1 weight.  With f = max(x, 0) per pixel of pair (i, n + i):
+ *   fh = f * (1 / (sqrt(sum_c f_c^2) + 1e-10)),   d = sum_c lin_w[c] * (fh_pred[c] - fh_target[c])^2      (fp32; channel sums in a fixed tree order)
+ *   acc[i] += (float)(sum over the pixels of d / (H W))                                                     (fp64, fixed order)
+ * so acc accumulates over the taps of a pair; the caller zeroes it before the first.  y_pool (nullable): receives max-pool(f) [2n][H / 2][W / 2][C], plain or
+ * PRE-SPLIT by split_out -- the bytes ssdnerf_relu_pool_nhwc(x, 2n, ..., pool = 1, split_out) writes.  workspace: ssdnerf_lpips_layer_workspace(n) bytes, 8-byte
+ * aligned, contents irrelevant on entry. */
+size_t ssdnerf_lpips_layer_workspace(uint32_t n);
+int ssdnerf_lpips_layer(const float* x, uint32_t n, uint32_t H, uint32_t W, uint32_t C, const float* lin_w, float* acc, void* y_pool, int split_out,
+                        void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

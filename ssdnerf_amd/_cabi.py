@@ -32,6 +32,7 @@ EXPORTS = [
     "ssdnerf_conv2d_nhwc_bf16_supported", "ssdnerf_conv2d_nhwc_bf16_plan", "ssdnerf_conv2d_nhwc_bf16", "ssdnerf_conv2d_nhwc_f32x2", "ssdnerf_conv2d_nhwc_f32x2_plan", "ssdnerf_attention_qkv_bf16", "ssdnerf_attention_qkv_f32", "ssdnerf_attention_qkv_f32_lse", "ssdnerf_attention_qkv_f32_backward", "ssdnerf_cam_rays", "ssdnerf_quantize_u8",
     "ssdnerf_marching_cubes_count", "ssdnerf_marching_cubes_emit", "ssdnerf_conv2d_nhwc_f32x2_presplit_supported", "ssdnerf_conv2d_nhwc_f32x2_presplit", "ssdnerf_split_f32_nhwc",
     "ssdnerf_image_metrics", "ssdnerf_tv_loss_forward", "ssdnerf_tv_loss_backward", "ssdnerf_mesh_vertex_attributes",
+    "ssdnerf_lpips_input", "ssdnerf_relu_pool_nhwc", "ssdnerf_lpips_layer_workspace", "ssdnerf_lpips_layer",
 ]
 
 
@@ -69,6 +70,12 @@ def lib() -> ctypes.CDLL:
                                                ctypes.c_void_p, ctypes.c_void_p]
         l.ssdnerf_mesh_vertex_attributes.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                                      ctypes.c_uint32, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float] + [ctypes.c_void_p] * 7
+        l.ssdnerf_lpips_input.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p]
+        l.ssdnerf_relu_pool_nhwc.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        l.ssdnerf_lpips_layer_workspace.restype = ctypes.c_size_t
+        l.ssdnerf_lpips_layer_workspace.argtypes = [ctypes.c_uint32]
+        l.ssdnerf_lpips_layer.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                          ctypes.c_void_p]
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -31,7 +31,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("SSDNERF_LIB_DIR") or os.path.join(HERE, "lib")     # SSDNERF_LIB_DIR + SSDNERF_EXTRA_FLAGS: side builds for A/B runs
 LIB_PATH = os.path.join(LIB_DIR, "libssdnerf_hip.so")
-SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "ddim.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip", "mesh_attr.hip"]
+SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "ddim.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip", "mesh_attr.hip", "lpips.hip"]
 LLVM_BIN = os.environ.get("SSDNERF_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TRANS_USE_WAIT_STATES = int(os.environ.get("SSDNERF_TRANS_USE_WAIT_STATES", "1"))     # 1 = the toolchain's own distance: the r03 rule is off (r06)
 SWAP_MFMA_WAIT_STATES = int(os.environ.get("SSDNERF_SWAP_MFMA_WAIT_STATES", "0"))    # asm_postpass.SWAP_MFMA_WAIT_STATES (0 = rule off: the default since r06)
@@ -42,8 +42,9 @@ VALIDATED_HIP_VERSIONS = ("7.2.",)              # prefixes of `hipcc --version`'
 FLAGS = os.environ.get("SSDNERF_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-result"]
 # per-source additions: OCML's powf, SLP-vectorised, leaves a packed fp32 add whose halves overwrite each other's source (the post-pass cannot
 # split it in place); tv_loss.hip is elementwise, so plain fp32 instructions cost it nothing measurable.  mesh_attr.hip: the same kind of instruction
-# comes out of the SLP-vectorised texel differences; one lane per mesh vertex, microseconds of work either way
-SOURCE_FLAGS = {"tv_loss.hip": ["-fno-slp-vectorize"], "mesh_attr.hip": ["-fno-slp-vectorize"]}
+# comes out of the SLP-vectorised texel differences; one lane per mesh vertex, microseconds of work either way.  lpips.hip: memory-bound passes whose
+# per-lane arithmetic is eight independent channels -- exactly what the SLP vectoriser packs -- and nothing there is bound by the vector ALU
+SOURCE_FLAGS = {"tv_loss.hip": ["-fno-slp-vectorize"], "mesh_attr.hip": ["-fno-slp-vectorize"], "lpips.hip": ["-fno-slp-vectorize"]}
 
 
 def _hipcc() -> str:

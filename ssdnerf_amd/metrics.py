@@ -1,7 +1,9 @@
 """Test-view scores of a reconstruction: PSNR and SSIM as the reference logs them (``eval_psnr`` / ``eval_ssim_skimage``,
 lib/core/evaluation/metrics.py:52-71, called by ``BaseNeRF.eval_and_viz``), both from one HIP launch (csrc/metrics.hip).
 
-LPIPS, the reference's third score, needs the ``lpips`` package and VGG weights; it is not computed, and ``use_lpips_metric`` has no effect."""
+LPIPS, the reference's third score (``eval_and_viz``, base_nerf.py:560-570), is ``image_lpips`` with a ``lpips.LPIPSVGG`` net: the VGG16 trunk on
+this library's convolution kernels and csrc/lpips.hip.  No weights ship with the project; a model computes the score when it has been given a net
+(``BaseNeRF.set_lpips`` or ``test_cfg['lpips_weights']``) and ``use_lpips_metric`` is set."""
 from __future__ import annotations
 
 import math
@@ -37,3 +39,9 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor) -> Tuple[torch.Tenso
                     "image_metrics")
     psnr = 10 * (2 * math.log10(1.0) - torch.log10(mse + 1e-6))
     return psnr, ssim
+
+
+def image_lpips(pred: torch.Tensor, target: torch.Tensor, net, chunk: int = 32) -> torch.Tensor:
+    """LPIPS v0.1 (VGG16) per image of two ``(..., h, w, 3)`` fp32 GPU tensors of equal shape with values in [0, 1], as an fp32 tensor of the leading
+    shape; ``net``: a ``lpips.LPIPSVGG``.  Same input rules as ``image_metrics``, with ``h, w >= 16``; ``chunk`` pairs pass through the trunk at a time."""
+    return net(pred, target, chunk=chunk)

@@ -55,6 +55,9 @@ class BaseNeRF(nn.Module):
         self.reg_loss = None if reg_loss is None else build_module(reg_loss)
         self.train_cfg, self.test_cfg = dict(train_cfg or {}), dict(test_cfg or {})
         self.update_extra_interval = update_extra_interval
+        # LPIPS of the test views: computed when this is set AND a net is present (set_lpips, or test_cfg['lpips_weights'] on first use).  The net
+        # lives in a plain list: not a submodule, so never part of state_dict() (the reference holds its lpips net the same way)
+        self.use_lpips_metric, self.lpips = use_lpips_metric, []
         self.init_scale, self.mean_ema_momentum, self.mean_scale = init_scale, mean_ema_momentum, mean_scale
         if init_from_mean:              # the running mean code of the stage-1 configs: a buffer (a plain attribute first would make it a KeyError)
             self.register_buffer("init_code", torch.zeros(self.code_size))
@@ -86,6 +89,19 @@ class BaseNeRF(nn.Module):
 
     def _modules_for_eval(self):
         return self.decoder_ema if self.decoder_use_ema else self.decoder
+
+    def set_lpips(self, net):
+        """attach (or with ``None`` detach) the ``lpips.LPIPSVGG`` that scores the test views"""
+        self.lpips[:] = [] if net is None else [net]
+
+    def _lpips_net(self):
+        """the attached net, or the one ``test_cfg['lpips_weights']`` names (loaded on first use); None without either or with ``use_lpips_metric`` unset"""
+        if not self.use_lpips_metric:
+            return None
+        if not self.lpips and self.test_cfg.get("lpips_weights"):
+            from .lpips import LPIPSVGG
+            self.lpips.append(LPIPSVGG.load(self.test_cfg["lpips_weights"]))
+        return self.lpips[0] if self.lpips else None
 
     # ---- scene files: {scene_name, param: {code | code_, density_grid (Morton fp16), density_bitfield (u8)}} -----------------------------
     def load_scene(self, data, load_density=False):
@@ -267,7 +283,9 @@ class BaseNeRF(nn.Module):
         """``test_poses`` rendered and quantised to k/255, and scored -> (log_vars, pred_imgs (S, V, 3, h, w) or None, extras).  As
         ``eval_and_viz`` (base_nerf.py:535-558): with ``test_imgs`` (S, V, h, w, 3) in the batch and ``test_cfg['skip_eval']`` unset, the views are
         rendered at the ground truth's size and scored against it -- ``log_vars`` holds ``test_psnr`` / ``test_ssim``, the means over all views, and
-        the extras ``test_metrics``, the per-view values as (S, V) device tensors (metrics.image_metrics).  LPIPS is not computed."""
+        the extras ``test_metrics``, the per-view values as (S, V) device tensors (metrics.image_metrics).  With ``use_lpips_metric`` and a net
+        (``set_lpips`` / ``test_cfg['lpips_weights']``) ``test_lpips`` and ``test_metrics['lpips']`` join them (metrics.image_lpips; base_nerf.py:560-570);
+        without a net nothing is added."""
         pred, log_vars, extra = None, dict(), dict()
         if "test_poses" in data:
             evaluate = "test_imgs" in data and not self.test_cfg.get("skip_eval", False)
@@ -275,9 +293,15 @@ class BaseNeRF(nn.Module):
             image, _ = self.render(decoder, code, density_bitfield, h, w, data["test_intrinsics"], data["test_poses"], cfg=self.test_cfg)
             image = torch.round(image.clamp(0, 1) * 255) / 255
             if evaluate:
-                psnr, ssim = image_metrics(image, data["test_imgs"].to(image.device, torch.float32))
+                target = data["test_imgs"].to(image.device, torch.float32)
+                psnr, ssim = image_metrics(image, target)
                 log_vars = dict(test_psnr=float(psnr.mean()), test_ssim=float(ssim.mean()))
                 extra["test_metrics"] = dict(psnr=psnr, ssim=ssim)
+                net = self._lpips_net()
+                if net is not None:
+                    lpips = net(image, target)
+                    log_vars.update(test_lpips=float(lpips.mean()))
+                    extra["test_metrics"].update(lpips=lpips)
             pred = image.permute(0, 1, 4, 2, 3)
         return log_vars, pred, extra
 

@@ -13,6 +13,8 @@ produced in this container, on the GPU box and on every rank (SURVEY.md section 
                            (``configs/paper_cfgs/ssdnerf_cars_uncond.py:39-50``), Xavier-uniform like
                            ``triplane_decoder.py:97-102`` plus a deliberate "shape pathway" so that
                            density is object-like instead of uniform fog.
+* ``make_lpips_params`` -- a state dict with the tensors of LPIPS v0.1 / VGG16 (``lpips.LPIPSVGG.from_state_dict``), seeded random: no pretrained
+                           weights exist here.
 * ``make_triplane``     -- a ``(3, 6, 128, 128)`` code in the ``TanhCode(scale=2)`` range whose
                            channel 0 carries three soft silhouettes (visual hull of a car-sized box)
                            and whose other channels are smooth noise.
@@ -116,3 +118,18 @@ def make_triplane(seed: int = 2021, variant: str = "object") -> torch.Tensor:
 
 def make_scene_batch(num_scenes: int, seed: int = 2021, variant: str = "object") -> torch.Tensor:
     return torch.stack([make_triplane(seed + s, variant) for s in range(num_scenes)], dim=0)
+
+
+def make_lpips_params(seed: int = 1) -> Dict[str, torch.Tensor]:
+    """A state dict with every tensor ``lpips.LPIPSVGG.from_state_dict`` takes, keyed like a torchvision ``vgg16`` (``features.<idx>.weight | bias``)
+    merged with the lpips package's ``lin<k>.model.1.weight``: convolution weights N(0, 2 / (9 Cin)) (activations keep their scale through
+    thirteen ReLU layers), biases U(-0.1, 0.1), lin weights U(0, 2 / C) (non-negative, as the trained ones are)."""
+    from .lpips import CHANNELS, FEATURE_IDX, TAP_CHANNELS
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for idx, (cin, cout) in zip(FEATURE_IDX, CHANNELS):
+        sd[f"features.{idx}.weight"] = torch.randn(cout, cin, 3, 3, generator=g) * math.sqrt(2.0 / (9 * cin))
+        sd[f"features.{idx}.bias"] = (torch.rand(cout, generator=g) - 0.5) * 0.2
+    for k, c in enumerate(TAP_CHANNELS):
+        sd[f"lin{k}.model.1.weight"] = (torch.rand(c, generator=g) * 2 / c).reshape(1, c, 1, 1)
+    return sd
