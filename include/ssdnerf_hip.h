@@ -502,6 +502,27 @@ size_t ssdnerf_lpips_layer_workspace(uint32_t n);
 int ssdnerf_lpips_layer(const float* x, uint32_t n, uint32_t H, uint32_t W, uint32_t C, const float* lin_w, float* acc, void* y_pool, int split_out,
                         void* workspace, void* stream);
 
+/* ---- FID / KID behind the feature extractor (csrc/feature_stats.hip; reference: FIDKID, lib/core/evaluation/metrics.py:135-215, which does this on the
+ * host with np.cov and float32 Gram matrices).  Both run on v_mfma_f64_16x16x4_f64: every fp32 feature is converted to fp64 once, products of two fp32
+ * values are exact in fp64, only the summation rounds.  No atomics, fixed summation orders: bit-identical from run to run.
+ *
+ * Moments of one contiguous (n, D) fp32 feature batch x, accumulated IN PLACE into fp64 sum [D] and outer [D][D] (the caller zeroes them before the first
+ * batch):   sum[i] += sum_k x[k][i],   outer[i][j] += sum_k x[k][i] x[k][j]   for the 64 x 64 tiles with tile_j >= tile_i only -- every element with
+ * j >= i is current, elements below the diagonal outside the diagonal tiles are never touched; the caller mirrors the upper triangle.  n == 0 is a no-op.
+ * Null accumulators, D == 0 or D > 2^20, a null x with n > 0 fail with SSDNERF_E_INVALID before any HIP call. */
+int ssdnerf_feature_moments_accumulate(const float* x, uint32_t n, uint32_t D, double* sum, double* outer, void* stream);
+/* The three kernel sums of KID per subset (FIDKID._calc_kid: (x x^T / D + 1)^3 etc.).  fake [Nf][D], real [Nr][D]: fp32 feature stores; idx_fake, idx_real
+ * [num_subsets][m] int64: the rows of each subset, in any order, repeats across subsets allowed; THE CALLER guarantees 0 <= idx < Nf / Nr (the device does
+ * not check).  With x_i = fake[idx_fake[s][i]], y_j = real[idx_real[s][j]]:
+ *   out[s][0] = Sxx = sum over positions i != j of (x_i . x_j / D + 1)^3      out[s][1] = Syy, the same over y
+ *   out[s][2] = Sxy = sum over all i, j of (x_i . y_j / D + 1)^3                                                  (fp64 [num_subsets][3])
+ * "i != j" is by POSITION in the subset: two positions that hold equal rows are counted.  workspace: ssdnerf_kid_subset_sums_workspace bytes, 8-byte
+ * aligned, contents irrelevant on entry (per-tile partial sums, added in a fixed order by a second pass).  Null pointers, num_subsets outside [1, 65535],
+ * m outside [2, 2^20], D == 0 fail with SSDNERF_E_INVALID, a short workspace with SSDNERF_E_WORKSPACE, before any HIP call. */
+size_t ssdnerf_kid_subset_sums_workspace(uint32_t num_subsets, uint32_t m);
+int ssdnerf_kid_subset_sums(const float* fake, const float* real, const int64_t* idx_fake, const int64_t* idx_real, uint32_t num_subsets, uint32_t m,
+                            uint32_t D, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,4 +7,5 @@ no CPU fallback for it.
 """
 from . import registry  # noqa: F401
 from . import decoders, diffusion, models, unet  # noqa: F401  (register module types)
-from .registry import MODELS, MODULES, build_module  # noqa: F401
+from . import fidkid  # noqa: F401  (registers the FIDKID metric)
+from .registry import METRICS, MODELS, MODULES, build_module  # noqa: F401

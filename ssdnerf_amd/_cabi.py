@@ -33,6 +33,7 @@ EXPORTS = [
     "ssdnerf_marching_cubes_count", "ssdnerf_marching_cubes_emit", "ssdnerf_conv2d_nhwc_f32x2_presplit_supported", "ssdnerf_conv2d_nhwc_f32x2_presplit", "ssdnerf_split_f32_nhwc",
     "ssdnerf_image_metrics", "ssdnerf_tv_loss_forward", "ssdnerf_tv_loss_backward", "ssdnerf_mesh_vertex_attributes",
     "ssdnerf_lpips_input", "ssdnerf_relu_pool_nhwc", "ssdnerf_lpips_layer_workspace", "ssdnerf_lpips_layer",
+    "ssdnerf_feature_moments_accumulate", "ssdnerf_kid_subset_sums_workspace", "ssdnerf_kid_subset_sums",
 ]
 
 
@@ -76,6 +77,10 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_lpips_layer_workspace.argtypes = [ctypes.c_uint32]
         l.ssdnerf_lpips_layer.argtypes = [ctypes.c_void_p] + [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
                                           ctypes.c_void_p]
+        l.ssdnerf_feature_moments_accumulate.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        l.ssdnerf_kid_subset_sums_workspace.restype = ctypes.c_size_t
+        l.ssdnerf_kid_subset_sums_workspace.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        l.ssdnerf_kid_subset_sums.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint32] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -8,7 +8,7 @@ import os
 import runpy
 from typing import Any, Dict
 
-from .registry import MODELS
+from .registry import METRICS, MODELS
 
 
 class ConfigDict(dict):
@@ -87,3 +87,18 @@ def _plain(v):
 def build_model(cfg: Config):
     import ssdnerf_amd.decoders, ssdnerf_amd.diffusion, ssdnerf_amd.models, ssdnerf_amd.unet  # noqa: F401  (populate the registries)
     return MODELS.build(_plain(cfg["model"]), default_args=dict(train_cfg=_plain(cfg.get("train_cfg", {})), test_cfg=_plain(cfg.get("test_cfg", {}))))
+
+
+def build_metrics(cfg) -> list:
+    """The metric objects of a config's ``evaluation`` block(s), as the reference's eval hook builds them (``build_metric`` over the ``metrics`` entry of
+    every ``dict(type='GenerativeEvalHook3D', ...)``): ``cfg.evaluation`` is a dict or a list of dicts, each ``metrics`` a dict or a list of dicts
+    (``dict(type='FIDKID', num_images=..., inception_pkl=..., inception_args=..., bgr2rgb=False)``).  Blocks without metrics contribute nothing."""
+    import ssdnerf_amd.fidkid  # noqa: F401  (populate the registry)
+    evaluation = cfg.get("evaluation") or []
+    blocks = evaluation if isinstance(evaluation, (list, tuple)) else [evaluation]
+    out = []
+    for block in blocks:
+        metrics = block.get("metrics") or []
+        for m in metrics if isinstance(metrics, (list, tuple)) else [metrics]:
+            out.append(METRICS.build(_plain(m)))
+    return out

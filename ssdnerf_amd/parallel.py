@@ -80,18 +80,41 @@ def weighted_log_vars(log_vars: dict, batch_sizes: List[int], device=None) -> di
     return out
 
 
-def evaluate_3d(model, batches, **sample_kwargs) -> dict:
-    """The scene-parallel evaluation loop of lib/apis/test.py:12-73, without the FID / IS feeding, the visualisation and the progress bar:
+def evaluate_3d(model, batches, metrics=None, feed_batch_size=32, **sample_kwargs) -> dict:
+    """The scene-parallel evaluation loop of lib/apis/test.py:12-73, without the visualisation and the progress bar:
     ``model.val_step(data, **sample_kwargs)`` on every batch of THIS rank (``batches``: an iterable of batch dicts, e.g. this rank's data
-    loader), then every logged scalar (``test_psnr``, ``test_ssim``) averaged over all scenes of all ranks by ``weighted_log_vars``."""
+    loader), then every logged scalar (``test_psnr``, ``test_ssim``) averaged over all scenes of all ranks by ``weighted_log_vars``.
+
+    ``metrics``: objects with ``feed(images, mode)`` / ``summary()`` / ``result_dict`` (``fidkid.FIDKID``; ``config.build_metrics``).  The rendered views
+    ``out['pred_imgs']`` (S, V, 3, h, w) in [0, 1] are fed ``feed_batch_size`` at a time as ``metric.feed(batch * 2 - 1, 'fakes')``, and ``data['test_imgs']``
+    (S, V, h, w, 3) as ``'reals'`` to the metrics that still want them (none once ``prepare()`` has loaded reference statistics); after the loop every
+    metric's ``summary()`` -- which reduces over the ranks itself -- joins the returned dict (``fid``, ``fid_mean``, ``fid_cov``, ``kid``)."""
     log_vars, batch_sizes = {}, []
+    metrics = list(metrics) if metrics else []
     for data in batches:
         out = model.val_step(data, **sample_kwargs)
         for key, value in out["log_vars"].items():
             log_vars.setdefault(key, []).append(value)
         batch_sizes.append(out["num_samples"])
+        if metrics:
+            pred = out["pred_imgs"]
+            fakes = pred.reshape(-1, *pred.shape[2:]).split(feed_batch_size, dim=0)
+            reals = None
+            for metric in metrics:
+                for b in fakes:
+                    metric.feed(b * 2 - 1, "fakes")
+                if "test_imgs" in data and getattr(metric, "wants", lambda mode: True)("reals"):
+                    if reals is None:
+                        real = data["test_imgs"].to(pred.device).permute(0, 1, 4, 2, 3)
+                        reals = real.reshape(-1, *real.shape[2:]).split(feed_batch_size, dim=0)
+                    for b in reals:
+                        metric.feed(b * 2 - 1, "reals")
     nccl = dist.is_available() and dist.is_initialized() and dist.get_backend() == "nccl"
-    return weighted_log_vars(log_vars, batch_sizes, device=torch.device("cuda", torch.cuda.current_device()) if nccl else None)
+    result = weighted_log_vars(log_vars, batch_sizes, device=torch.device("cuda", torch.cuda.current_device()) if nccl else None)
+    for metric in metrics:
+        metric.summary()
+        result.update(metric.result_dict)
+    return result
 
 
 # ---------------------------------------------------------------------------------------------- second axis: views (SURVEY.md section 8(e): "#scenes < #GPUs")

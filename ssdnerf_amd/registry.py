@@ -46,6 +46,7 @@ class Registry:
 
 MODULES = Registry("module")
 MODELS = MODULES  # mmgen aliases the two (mmgen/models/builder.py)
+METRICS = Registry("metric")  # mmgen.core.registry.METRICS: what an ``evaluation`` block's ``metrics=dict(type='FIDKID', ...)`` is built from
 
 
 def build_module(cfg, default_args=None):
