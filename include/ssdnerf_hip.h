@@ -314,6 +314,33 @@ int ssdnerf_image_metrics(const float* a, const float* b, uint32_t n, uint32_t h
 int ssdnerf_tv_loss_forward(const float* x, uint32_t n, uint32_t h, uint32_t w, float power, float* slice_mean, void* stream);
 int ssdnerf_tv_loss_backward(const float* x, const float* g, uint32_t n, uint32_t h, uint32_t w, float power, float* dx_out, void* stream);
 
+/* One Adam step of T fp32 tensors in ONE launch: the per-scene code leaves of stage-1 fitting and the decoder's weights (the reference's
+ * optimizer: torch.optim.Adam, amsgrad=False, maximize=False, the non-capturable single-tensor form).  Per element of tensor k, in fp32:
+ *   g <- grad + weight_decay * param           only when weight_decay != 0 (L2 in the gradient, not decoupled decay)
+ *   exp_avg    <- exp_avg + (g - exp_avg) (1 - beta1)
+ *   exp_avg_sq <- exp_avg_sq beta2 + (1 - beta2) g g
+ *   param      <- param - step_size * exp_avg / (sqrt(exp_avg_sq) / bc2_sqrt + eps)
+ * step_size = lr / (1 - beta1^step) and bc2_sqrt = sqrt(1 - beta2^step) are PER TENSOR (scenes out of the cache carry their own step counts,
+ * an LR schedule per optimizer its own learning rate): the caller forms them in double for the step being taken and passes them as float.
+ * beta1, beta2 and eps are common to the call; 1 - beta1 and 1 - beta2 are formed in double here.  NaN / Inf gradients propagate.
+ * `tensors` is a HOST array that is read before the call returns (it travels in the kernel arguments); param, exp_avg and exp_avg_sq are
+ * updated in place, grad is only read, and no element outside [0, numel) of any array is touched.  16-byte loads and stores where a
+ * tensor's four pointers are 16-byte aligned, element by element otherwise (4-byte alignment is required).
+ * No host synchronisation, no allocation, no workspace.  A null pointer, T == 0, T > SSDNERF_ADAM_MAX_TENSORS (split longer lists over
+ * several calls), numel == 0 or > 2^40 and a misaligned pointer fail with SSDNERF_E_INVALID before any HIP call. */
+#define SSDNERF_ADAM_MAX_TENSORS 32
+typedef struct ssdnerf_adam_tensor {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    uint64_t numel;
+    float step_size, bc2_sqrt, weight_decay;
+    uint32_t reserved; /* pads the entry to 56 bytes */
+} ssdnerf_adam_tensor;
+uint32_t ssdnerf_adam_max_tensors(void);
+int ssdnerf_adam_step_multi(const ssdnerf_adam_tensor* tensors, uint32_t T, double beta1, double beta2, double eps, void* stream);
+
 /* ---- Part 3: denoising-UNet glue (lib/models/architecture/ddpm/modules.py:12-129, denoising.py:178-187) ------------------
  * Activations are channel-last: x, y are [B][HW][C] of dtype 0 = fp32, 1 = fp16, 2 = bf16.
  *

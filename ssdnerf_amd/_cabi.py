@@ -34,7 +34,15 @@ EXPORTS = [
     "ssdnerf_image_metrics", "ssdnerf_tv_loss_forward", "ssdnerf_tv_loss_backward", "ssdnerf_mesh_vertex_attributes",
     "ssdnerf_lpips_input", "ssdnerf_relu_pool_nhwc", "ssdnerf_lpips_layer_workspace", "ssdnerf_lpips_layer",
     "ssdnerf_feature_moments_accumulate", "ssdnerf_kid_subset_sums_workspace", "ssdnerf_kid_subset_sums",
+    "ssdnerf_adam_max_tensors", "ssdnerf_adam_step_multi",
 ]
+
+
+class AdamTensor(ctypes.Structure):
+    """``ssdnerf_adam_tensor`` (include/ssdnerf_hip.h): one row of the table ``ssdnerf_adam_step_multi`` steps in a launch"""
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
+                ("numel", ctypes.c_uint64), ("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float), ("weight_decay", ctypes.c_float),
+                ("reserved", ctypes.c_uint32)]
 
 
 def lib_path() -> str:
@@ -81,6 +89,9 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_kid_subset_sums_workspace.restype = ctypes.c_size_t
         l.ssdnerf_kid_subset_sums_workspace.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
         l.ssdnerf_kid_subset_sums.argtypes = [ctypes.c_void_p] * 4 + [ctypes.c_uint32] * 3 + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
+        l.ssdnerf_adam_max_tensors.restype = ctypes.c_uint32
+        l.ssdnerf_adam_max_tensors.argtypes = []
+        l.ssdnerf_adam_step_multi.argtypes = [ctypes.POINTER(AdamTensor), ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -23,6 +23,7 @@ from typing import Dict, Iterator, List, Optional, Sequence, Union
 import torch
 
 from . import nerf
+from .optim import step_all
 
 
 @dataclass
@@ -128,8 +129,7 @@ class CodeFitter:
             for leaf, g in zip(self._leaves(), seeds):
                 leaf.grad.copy_(g)
         loss.backward()
-        for opt in self.optimizers:
-            opt.step()
+        step_all(self.optimizers)
         for sch in self.schedulers:
             sch.step()
         self.k += 1

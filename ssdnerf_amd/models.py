@@ -30,13 +30,17 @@ from .codes import IdentityCode, MSELoss, NormalizedTanhCode, RegLoss, TanhCode,
 from .density import get_density as _get_density, update_density_grid
 from .fitting import CodeFitter, Conditioning, GuidanceObjective, RayBatcher
 from .metrics import image_metrics
+from .optim import HIPAdam, step_all
 from .registry import MODELS, build_module, get_module_device
 
 
 def _torch_factory(namespace, cfg: Dict):
-    """``dict(type='Adam', lr=...)`` -> (torch class, kwargs)"""
+    """``dict(type='Adam', lr=...)`` -> (torch class, kwargs); ``type='HIPAdam'`` is this package's optimizer (optim.py)"""
     kw = dict(cfg)
-    return getattr(namespace, kw.pop("type")), kw
+    name = kw.pop("type")
+    if name == "HIPAdam":
+        return HIPAdam, kw
+    return getattr(namespace, name), kw
 
 
 class BaseNeRF(nn.Module):
@@ -445,10 +449,7 @@ class MultiSceneNeRF(BaseNeRF):
             for leaf, g in zip(leaves, seed_grads):
                 leaf.grad.copy_(g)
         loss.backward()
-        if "decoder" in optimizer:
-            optimizer["decoder"].step()
-        for opt in code_optimizers:
-            opt.step()
+        step_all(([optimizer["decoder"]] if "decoder" in optimizer else []) + list(code_optimizers))
         self.save_cache(leaves, code_optimizers, density_grid, density_bitfield, data["scene_id"], data["scene_name"])
         with torch.no_grad():
             if code_optimizers:
