@@ -341,6 +341,19 @@ typedef struct ssdnerf_adam_tensor {
 uint32_t ssdnerf_adam_max_tensors(void);
 int ssdnerf_adam_step_multi(const ssdnerf_adam_tensor* tensors, uint32_t T, double beta1, double beta2, double eps, void* stream);
 
+/* A batch of views out of a device-resident uint8 image store, as the fp32 the reference's dataset hands out
+ * (lib/datasets/shapenet_srn.py:160: `img.astype(np.float32) / 255`), in one launch (csrc/scene_store.hip; datasets.SceneStore.gather):
+ *   out[k][b] = (float)store[index[k]][b] / 255.0f      k < count, b < image_bytes
+ * store: num_images images of image_bytes = h * w * 3 bytes each, back to back (any alignment); index: count int32 ON THE DEVICE, each in
+ * [0, num_images) -- NOT checked here, the caller validates them on the host; out: count * image_bytes fp32, contiguous.
+ * The division is IEEE fp32, so every value is numpy's quotient bit for bit.  Where image_bytes % 16 == 0 and store and out are 16-byte aligned
+ * a lane reads 4 bytes per load and writes them as one 16-byte non-temporal store; element by element otherwise.  store and index are only
+ * read, nothing outside out's count * image_bytes elements is written.  No host synchronisation, no allocation, no workspace.  A null pointer,
+ * count == 0, image_bytes == 0, num_images == 0 or >= 2^31, count * image_bytes > 2^40 and an index or out that is not 4-byte aligned fail with
+ * SSDNERF_E_INVALID before any HIP call. */
+int ssdnerf_gather_views_u8(const uint8_t* store, uint64_t image_bytes, uint64_t num_images, const int32_t* index, uint64_t count, float* out,
+                            void* stream);
+
 /* ---- Part 3: denoising-UNet glue (lib/models/architecture/ddpm/modules.py:12-129, denoising.py:178-187) ------------------
  * Activations are channel-last: x, y are [B][HW][C] of dtype 0 = fp32, 1 = fp16, 2 = bf16.
  *

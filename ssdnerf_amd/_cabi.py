@@ -35,6 +35,7 @@ EXPORTS = [
     "ssdnerf_lpips_input", "ssdnerf_relu_pool_nhwc", "ssdnerf_lpips_layer_workspace", "ssdnerf_lpips_layer",
     "ssdnerf_feature_moments_accumulate", "ssdnerf_kid_subset_sums_workspace", "ssdnerf_kid_subset_sums",
     "ssdnerf_adam_max_tensors", "ssdnerf_adam_step_multi",
+    "ssdnerf_gather_views_u8",
 ]
 
 
@@ -92,6 +93,7 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_adam_max_tensors.restype = ctypes.c_uint32
         l.ssdnerf_adam_max_tensors.argtypes = []
         l.ssdnerf_adam_step_multi.argtypes = [ctypes.POINTER(AdamTensor), ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]
+        l.ssdnerf_gather_views_u8.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -102,3 +102,15 @@ def build_metrics(cfg) -> list:
         for m in metrics if isinstance(metrics, (list, tuple)) else [metrics]:
             out.append(METRICS.build(_plain(m)))
     return out
+
+
+def build_dataset(cfg, default_args=None):
+    """A ``data`` block's entry (``cfg.data.train`` / ``val_cond`` / ``val_uncond``: ``dict(type='ShapeNetSRN', ...)``) -> the dataset (datasets.py)"""
+    from .datasets import build_dataset as build
+    return build(cfg, default_args)
+
+
+def build_dataloader(dataset, samples_per_gpu, **kwargs):
+    """This rank's in-process loader of batch dicts over a device-resident image store (``datasets.build_dataloader``)"""
+    from .datasets import build_dataloader as build
+    return build(dataset, samples_per_gpu, **kwargs)

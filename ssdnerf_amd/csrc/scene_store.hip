@@ -1,0 +1,121 @@
+// ssdnerf_amd/csrc/scene_store.hip -- a batch of views out of the device-resident image store (datasets.SceneStore): the images of a dataset
+// are kept as uint8, back to back; one launch picks `count` of them by index and writes them as the fp32 the fitting code reads,
+//     out[k][b] = (float)store[index[k]][b] / 255.0f,
+// which is what the reference's dataset computes per image on the host (lib/datasets/shapenet_srn.py:160, numpy `astype(float32) / 255`).
+//
+// Arithmetic: ONE IEEE fp32 division per element (the library is built with -fno-fast-math; hipcc's fp32 division is correctly rounded), so
+// the result is numpy's quotient bit for bit for all 256 byte values.  `x * (1 / 255.f)` is NOT: it differs at 126 of the 256 values.
+//
+// Shape: a pure stream, 1 byte in and 4 bytes out per element, no LDS, no atomics.  The output is one array of count * image_bytes elements; a
+// block of GV_THREADS lanes owns GV_CHUNK consecutive ones.  Every lane finds the image of its elements by integer division of the element
+// offset (a chunk may span several small images, and an image many chunks).
+//   vector path  (image_bytes % 16 == 0, store and out 16-byte aligned: the 128 x 128 and 64 x 64 views): a lane takes 4 * GV_GROUPS groups of 4
+//                consecutive source bytes, GV_THREADS * 4 apart -- one 4-byte load each, all issued before the first use -- and writes each group
+//                as one 16-byte non-temporal store, so a wave's store instruction covers 1 KB of `out` without gaps.  A group never straddles an
+//                image, because image_bytes is a multiple of 4.  Measured on the training batch, 8 x 50 views of 128 x 128 (profiles/dataset.json,
+//                DESIGN.md section 16): about 16 us, against 19 us with plain stores (-DGV_PLAIN_STORES), 29 us for one 16-byte load and four
+//                16-byte stores per lane with plain stores (-DGV_LOAD16 -DGV_PLAIN_STORES: every store instruction of a wave then writes 16
+//                of every 64 bytes) and 106 us for that form with non-temporal stores (-DGV_LOAD16).
+//   element path (everything else: 5 x 7 x 3 = 105-byte images, whose starts are misaligned, or a store pointer that is only 1-byte aligned):
+//                consecutive lanes take consecutive elements, under `i < total`.
+// `store` and `index` are only read; nothing outside [0, count * image_bytes) of `out` is written.  The indices are NOT checked here: the Python
+// layer validates them on the host before it uploads them.
+#include "common.h"
+
+#define GV_THREADS 256
+#define GV_GROUPS 2
+#define GV_CHUNK (GV_THREADS * 16 * GV_GROUPS)          // elements per block (8192)
+
+#ifdef GV_PLAIN_STORES                                   // A/B builds only
+#define GV_STORE4(p, v) (*(p) = (v))
+#else                                                    // the output is written once and read by later kernels
+#define GV_STORE4(p, v) __builtin_nontemporal_store((v), (p))
+#endif
+
+typedef float gv_float4 __attribute__((ext_vector_type(4)));
+
+SSD_DEV float gv_unit(uint32_t byte) { return (float)byte / 255.0f; }
+
+SSD_DEV gv_float4 gv_unit4(uint32_t word) {
+    gv_float4 r;
+    r.x = gv_unit(word & 0xffu);
+    r.y = gv_unit((word >> 8) & 0xffu);
+    r.z = gv_unit((word >> 16) & 0xffu);
+    r.w = gv_unit(word >> 24);
+    return r;
+}
+
+__global__ void __launch_bounds__(GV_THREADS) k_gather_views_u8_vec(const uint8_t* __restrict__ store, uint64_t image_bytes, const int32_t* __restrict__ index,
+                                                                    uint64_t total, float* __restrict__ out) {
+    const uint64_t base = (uint64_t)blockIdx.x * GV_CHUNK;
+#ifndef GV_LOAD16
+    uint32_t word[GV_GROUPS * 4];
+    uint64_t ew[GV_GROUPS * 4];
+#pragma unroll
+    for (int g = 0; g < GV_GROUPS * 4; ++g) {
+        ew[g] = base + (uint64_t)(g * GV_THREADS + threadIdx.x) * 4;
+        if (ew[g] < total) {
+            const uint64_t k = ew[g] / image_bytes;
+            const uint64_t b = ew[g] - k * image_bytes;
+            word[g] = *reinterpret_cast<const uint32_t*>(store + (uint64_t)index[k] * image_bytes + b);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < GV_GROUPS * 4; ++g)
+        if (ew[g] < total) GV_STORE4(reinterpret_cast<gv_float4*>(out + ew[g]), gv_unit4(word[g]));
+#else                                                    // A/B builds only: one 16-byte load and four 16-byte stores per lane and group
+    uint4 src[GV_GROUPS];
+    uint64_t e[GV_GROUPS];
+#pragma unroll
+    for (int g = 0; g < GV_GROUPS; ++g) {
+        e[g] = base + (uint64_t)(g * GV_THREADS + threadIdx.x) * 16;
+        if (e[g] < total) {                                          // total is a multiple of 16: a group is whole or absent
+            const uint64_t k = e[g] / image_bytes;
+            const uint64_t b = e[g] - k * image_bytes;
+            src[g] = *reinterpret_cast<const uint4*>(store + (uint64_t)index[k] * image_bytes + b);
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < GV_GROUPS; ++g) {
+        if (e[g] < total) {
+            gv_float4* dst = reinterpret_cast<gv_float4*>(out + e[g]);
+            GV_STORE4(dst + 0, gv_unit4(src[g].x));
+            GV_STORE4(dst + 1, gv_unit4(src[g].y));
+            GV_STORE4(dst + 2, gv_unit4(src[g].z));
+            GV_STORE4(dst + 3, gv_unit4(src[g].w));
+        }
+    }
+#endif
+}
+
+__global__ void __launch_bounds__(GV_THREADS) k_gather_views_u8_elem(const uint8_t* __restrict__ store, uint64_t image_bytes, const int32_t* __restrict__ index,
+                                                                     uint64_t total, float* __restrict__ out) {
+    const uint64_t base = (uint64_t)blockIdx.x * GV_CHUNK;
+    for (int j = 0; j < GV_CHUNK / GV_THREADS; ++j) {
+        const uint64_t i = base + (uint64_t)(j * GV_THREADS + threadIdx.x);
+        if (i < total) {
+            const uint64_t k = i / image_bytes;
+            const uint64_t b = i - k * image_bytes;
+            out[i] = gv_unit(store[(uint64_t)index[k] * image_bytes + b]);
+        }
+    }
+}
+
+extern "C" int ssdnerf_gather_views_u8(const uint8_t* store, uint64_t image_bytes, uint64_t num_images, const int32_t* index, uint64_t count, float* out,
+                                       void* stream) {
+    SSD_REQUIRE(store != nullptr && index != nullptr && out != nullptr, "gather_views_u8: null pointer");
+    SSD_REQUIRE(count > 0, "gather_views_u8: count == 0 (no views)");
+    SSD_REQUIRE(image_bytes > 0, "gather_views_u8: image_bytes == 0");
+    SSD_REQUIRE(num_images > 0, "gather_views_u8: num_images == 0 (an empty store)");
+    SSD_REQUIRE(num_images <= 0x7fffffffull, "gather_views_u8: %llu images, the int32 indices reach 2^31 - 1", (unsigned long long)num_images);
+    const uint64_t limit = (uint64_t)1 << 40;
+    SSD_REQUIRE(image_bytes <= limit && count <= limit / image_bytes, "gather_views_u8: count * image_bytes is more than 2^40 elements");
+    SSD_REQUIRE((((uintptr_t)index | (uintptr_t)out) & 3u) == 0, "gather_views_u8: index or out is not 4-byte aligned");
+    const uint64_t total = count * image_bytes;
+    const uint32_t blocks = (uint32_t)((total + GV_CHUNK - 1) / GV_CHUNK);      // <= 2^27
+    const bool vec = image_bytes % 16 == 0 && (((uintptr_t)store | (uintptr_t)out) & 15u) == 0;
+    if (vec) hipLaunchKernelGGL(k_gather_views_u8_vec, dim3(blocks), dim3(GV_THREADS), 0, (hipStream_t)stream, store, image_bytes, index, total, out);
+    else hipLaunchKernelGGL(k_gather_views_u8_elem, dim3(blocks), dim3(GV_THREADS), 0, (hipStream_t)stream, store, image_bytes, index, total, out);
+    SSD_CHECK_LAUNCH("gather_views_u8");
+    return SSDNERF_OK;
+}

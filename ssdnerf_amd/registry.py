@@ -47,6 +47,7 @@ class Registry:
 MODULES = Registry("module")
 MODELS = MODULES  # mmgen aliases the two (mmgen/models/builder.py)
 METRICS = Registry("metric")  # mmgen.core.registry.METRICS: what an ``evaluation`` block's ``metrics=dict(type='FIDKID', ...)`` is built from
+DATASETS = Registry("dataset")  # mmgen.datasets.builder.DATASETS: what a ``data`` block's ``dict(type='ShapeNetSRN', ...)`` entries are built from
 
 
 def build_module(cfg, default_args=None):
