@@ -341,6 +341,33 @@ typedef struct ssdnerf_adam_tensor {
 uint32_t ssdnerf_adam_max_tensors(void);
 int ssdnerf_adam_step_multi(const ssdnerf_adam_tensor* tensors, uint32_t T, double beta1, double beta2, double eps, void* stream);
 
+/* The EMA copies of the trained modules (the reference's ExponentialMovingAverageHook with interp_mode='lerp': custom_hooks[0] of every training
+ * config) updated in ONE launch over a device-resident plan (csrc/ema.hip, arithmetic in csrc/ema_math.h; ssdnerf_amd/ema.py).  Per element of row k:
+ *   dst <- fl32( src + fl32( fl32(dst - src) * m ) ),   m = momentum where the row's `trainable` is 1, momentum_nontrainable where it is 0
+ * three separately rounded fp32 operations (what eager `src + (ema - src) * m` computes; not torch.lerp), denormals kept, NaN / Inf propagate.
+ *
+ * ssdnerf_ema_plan_build works on a HOST array of T rows: it validates them and fills in first_block (the prefix sum of the rows' block
+ * counts, ssdnerf_ema_chunk() elements per block) and *blocks_out, the grid of the launch.  It fails with SSDNERF_E_INVALID -- and makes no HIP
+ * call either way -- on a null pointer, T == 0 or > SSDNERF_EMA_MAX_ROWS, numel == 0 or > 2^40, a pointer that is not 4-byte aligned, a
+ * trainable flag other than 0 / 1, more than 2^31 - 1 blocks, a dst that appears twice, and a dst range that overlaps any dst or src range
+ * (src ranges may overlap each other).  The caller copies the completed rows to device memory it owns: that is the plan, valid for as long as
+ * the pointers in it are.  The library allocates no device memory and keeps no reference to the rows or the plan.
+ *
+ * ssdnerf_ema_update_multi launches over a plan ON THE DEVICE (8-byte aligned) with the T and block count plan_build returned: dst is updated
+ * in place, src is only read, no element outside [0, numel) of any array is touched; 16-byte loads and stores where both pointers of a row
+ * are 16-byte aligned, element by element otherwise.  No host synchronisation, no allocation, no workspace. */
+#define SSDNERF_EMA_MAX_ROWS (1u << 20)
+typedef struct ssdnerf_ema_row {
+    const float* src;
+    float* dst;
+    uint64_t numel;
+    uint32_t trainable;   /* 1: the source requires grad (momentum); 0: buffer or frozen parameter (momentum_nontrainable) */
+    uint32_t first_block; /* written by ssdnerf_ema_plan_build */
+} ssdnerf_ema_row;
+uint32_t ssdnerf_ema_chunk(void);
+int ssdnerf_ema_plan_build(ssdnerf_ema_row* rows, uint32_t T, uint32_t* blocks_out);
+int ssdnerf_ema_update_multi(const ssdnerf_ema_row* plan, uint32_t T, uint32_t blocks, float momentum, float momentum_nontrainable, void* stream);
+
 /* A batch of views out of a device-resident uint8 image store, as the fp32 the reference's dataset hands out
  * (lib/datasets/shapenet_srn.py:160: `img.astype(np.float32) / 255`), in one launch (csrc/scene_store.hip; datasets.SceneStore.gather):
  *   out[k][b] = (float)store[index[k]][b] / 255.0f      k < count, b < image_bytes

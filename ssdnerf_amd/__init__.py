@@ -8,4 +8,5 @@ no CPU fallback for it.
 from . import registry  # noqa: F401
 from . import decoders, diffusion, models, unet  # noqa: F401  (register module types)
 from . import fidkid  # noqa: F401  (registers the FIDKID metric)
-from .registry import METRICS, MODELS, MODULES, build_module  # noqa: F401
+from . import ema  # noqa: F401  (registers ExponentialMovingAverageHook)
+from .registry import HOOKS, METRICS, MODELS, MODULES, build_hook, build_module  # noqa: F401

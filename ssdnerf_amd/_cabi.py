@@ -36,6 +36,7 @@ EXPORTS = [
     "ssdnerf_feature_moments_accumulate", "ssdnerf_kid_subset_sums_workspace", "ssdnerf_kid_subset_sums",
     "ssdnerf_adam_max_tensors", "ssdnerf_adam_step_multi",
     "ssdnerf_gather_views_u8",
+    "ssdnerf_ema_chunk", "ssdnerf_ema_plan_build", "ssdnerf_ema_update_multi",
 ]
 
 
@@ -44,6 +45,12 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p),
                 ("numel", ctypes.c_uint64), ("step_size", ctypes.c_float), ("bc2_sqrt", ctypes.c_float), ("weight_decay", ctypes.c_float),
                 ("reserved", ctypes.c_uint32)]
+
+
+class EmaRow(ctypes.Structure):
+    """``ssdnerf_ema_row`` (include/ssdnerf_hip.h): one (source, EMA) tensor pair of the plan ``ssdnerf_ema_update_multi`` launches over"""
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("numel", ctypes.c_uint64), ("trainable", ctypes.c_uint32),
+                ("first_block", ctypes.c_uint32)]
 
 
 def lib_path() -> str:
@@ -94,6 +101,10 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_adam_max_tensors.argtypes = []
         l.ssdnerf_adam_step_multi.argtypes = [ctypes.POINTER(AdamTensor), ctypes.c_uint32, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p]
         l.ssdnerf_gather_views_u8.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
+        l.ssdnerf_ema_chunk.restype = ctypes.c_uint32
+        l.ssdnerf_ema_chunk.argtypes = []
+        l.ssdnerf_ema_plan_build.argtypes = [ctypes.POINTER(EmaRow), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
+        l.ssdnerf_ema_update_multi.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

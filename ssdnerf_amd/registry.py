@@ -48,6 +48,12 @@ MODULES = Registry("module")
 MODELS = MODULES  # mmgen aliases the two (mmgen/models/builder.py)
 METRICS = Registry("metric")  # mmgen.core.registry.METRICS: what an ``evaluation`` block's ``metrics=dict(type='FIDKID', ...)`` is built from
 DATASETS = Registry("dataset")  # mmgen.datasets.builder.DATASETS: what a ``data`` block's ``dict(type='ShapeNetSRN', ...)`` entries are built from
+HOOKS = Registry("hook")  # mmcv.runner.HOOKS: what a config's ``custom_hooks`` entries (``dict(type='ExponentialMovingAverageHook', ...)``) are built from
+
+
+def build_hook(cfg, default_args=None):
+    """one ``custom_hooks`` entry -> the hook object (mmcv's ``build_from_cfg(cfg, HOOKS)``); ``priority`` stays an argument of the hook"""
+    return HOOKS.build(cfg, default_args)
 
 
 def build_module(cfg, default_args=None):
