@@ -381,6 +381,22 @@ int ssdnerf_ema_update_multi(const ssdnerf_ema_row* plan, uint32_t T, uint32_t b
 int ssdnerf_gather_views_u8(const uint8_t* store, uint64_t image_bytes, uint64_t num_images, const int32_t* index, uint64_t count, float* out,
                             void* stream);
 
+/* R sampled pixels per scene out of the same store, each with its camera ray, in one launch (csrc/scene_store.hip; datasets.StoredViews.sample):
+ * what fitting.RayBatcher draws for a training step, without the fp32 views or the (S, V, h, w, 3) ray arrays ever being written.
+ *   store: num_images images of h * w * 3 bytes, back to back;  view_image [S][V]: the image of view v of scene s, int32 ON THE DEVICE, each in
+ *   [0, num_images) -- NOT checked here, the caller validates the table on the host;  c2w [S][V][16] row-major, intr [S][V][4] = {fx, fy, cx, cy};
+ *   inds [S][R] int64 (what torch.randperm gives): pixel p in [0, V * h * w) of the scene, view p / (h*w), pixel q = p % (h*w) at (q % w, q / w);
+ *   inds == NULL: p = r, every pixel in order, and R must be V * h * w.
+ *   rays_o, rays_d, target [S][R][3]: the ray of that pixel by the arithmetic of ssdnerf_cam_rays and its colour byte / 255 by the arithmetic of
+ *   ssdnerf_gather_views_u8 -- the same device functions, so all nine floats equal, bit for bit, what those two calls followed by indexing give.
+ * A p outside [0, V * h * w) reads nothing and makes that ray's nine floats NaN; no other ray is affected.  Inputs are only read, nothing outside
+ * the S * R * 3 elements of each output is written.  No host synchronisation, no allocation, no workspace.  A null pointer (other than inds),
+ * S, V, R, h or w == 0, V * h * w >= 2^32, num_images == 0 or >= 2^31, S * R > 2^38, inds == NULL with R != V * h * w, an output or table that is
+ * not 4-byte aligned and an inds that is not 8-byte aligned fail with SSDNERF_E_INVALID before any HIP call. */
+int ssdnerf_sample_rays_u8(const uint8_t* store, uint64_t num_images, uint32_t h, uint32_t w, const int32_t* view_image, const float* c2w,
+                           const float* intr, uint32_t S, uint32_t V, const int64_t* inds, uint32_t R, float* rays_o, float* rays_d, float* target,
+                           void* stream);
+
 /* ---- Part 3: denoising-UNet glue (lib/models/architecture/ddpm/modules.py:12-129, denoising.py:178-187) ------------------
  * Activations are channel-last: x, y are [B][HW][C] of dtype 0 = fp32, 1 = fp16, 2 = bf16.
  *

@@ -20,6 +20,13 @@
 //                consecutive lanes take consecutive elements, under `i < total`.
 // `store` and `index` are only read; nothing outside [0, count * image_bytes) of `out` is written.  The indices are NOT checked here: the Python
 // layer validates them on the host before it uploads them.
+//
+// k_sample_rays_u8 (ssdnerf_sample_rays_u8, datasets.StoredViews.sample) is the other way out of the store: not whole views but R sampled PIXELS
+// per scene, each with its camera ray -- what fitting.RayBatcher hands to the renderer -- so that a training batch never exists as fp32 images
+// and (S, V, h, w, 3) ray arrays.  One lane per ray: the pixel index picks the view, ssd_cam_ray (common.h) makes the ray from that view's pose
+// and intrinsics, gv_unit (below) makes the colour from the pixel's three bytes; the same two functions the dense kernels call, so all nine
+// floats are the dense path's bit for bit.  No LDS, no atomics; the pose table (S * V * 80 B) is a per-lane load that stays in cache, the
+// bytes are a random gather, 36 B are written per lane.  About 1.3 MB moves at the training batch (8 x 4096 rays): launch-bound.
 #include "common.h"
 
 #define GV_THREADS 256
@@ -117,5 +124,56 @@ extern "C" int ssdnerf_gather_views_u8(const uint8_t* store, uint64_t image_byte
     if (vec) hipLaunchKernelGGL(k_gather_views_u8_vec, dim3(blocks), dim3(GV_THREADS), 0, (hipStream_t)stream, store, image_bytes, index, total, out);
     else hipLaunchKernelGGL(k_gather_views_u8_elem, dim3(blocks), dim3(GV_THREADS), 0, (hipStream_t)stream, store, image_bytes, index, total, out);
     SSD_CHECK_LAUNCH("gather_views_u8");
+    return SSDNERF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// sampled pixels of a batch's views, with their rays: out[s][r] for pixel p = inds[s][r] (or r, inds == NULL) of scene s, p = view * hw + pixel
+#define RS_THREADS 256
+
+__global__ void __launch_bounds__(RS_THREADS) k_sample_rays_u8(const uint8_t* __restrict__ store, uint32_t hw, uint32_t w, const int32_t* __restrict__ view_image,
+                                                               const float* __restrict__ c2w, const float* __restrict__ intr, uint32_t V,
+                                                               const int64_t* __restrict__ inds, uint32_t R, uint64_t total, float* __restrict__ rays_o,
+                                                               float* __restrict__ rays_d, float* __restrict__ target) {
+    const uint64_t i = (uint64_t)blockIdx.x * RS_THREADS + threadIdx.x;
+    if (i >= total) return;
+    const uint64_t s = i / R;
+    const int64_t p = inds != nullptr ? inds[i] : (int64_t)(i - s * R);
+    float o[3], d[3], c[3];
+    if ((uint64_t)p < (uint64_t)V * hw) {                            // (a negative p is a huge unsigned one)
+        const uint32_t v = (uint32_t)p / hw, q = (uint32_t)p - v * hw;
+        const uint64_t cam = s * V + v;
+        ssd_cam_ray(c2w + cam * 16, intr + cam * 4, q % w, q / w, o, d);
+        const uint8_t* px = store + ((uint64_t)view_image[cam] * hw + q) * 3;
+        c[0] = gv_unit(px[0]); c[1] = gv_unit(px[1]); c[2] = gv_unit(px[2]);
+    } else {                                                         // outside the views: nothing is read, the ray is NaN
+        const float nan = __builtin_nanf("");
+        o[0] = o[1] = o[2] = d[0] = d[1] = d[2] = c[0] = c[1] = c[2] = nan;
+    }
+    rays_o[3 * i + 0] = o[0]; rays_o[3 * i + 1] = o[1]; rays_o[3 * i + 2] = o[2];
+    rays_d[3 * i + 0] = d[0]; rays_d[3 * i + 1] = d[1]; rays_d[3 * i + 2] = d[2];
+    target[3 * i + 0] = c[0]; target[3 * i + 1] = c[1]; target[3 * i + 2] = c[2];
+}
+
+extern "C" int ssdnerf_sample_rays_u8(const uint8_t* store, uint64_t num_images, uint32_t h, uint32_t w, const int32_t* view_image, const float* c2w,
+                                      const float* intr, uint32_t S, uint32_t V, const int64_t* inds, uint32_t R, float* rays_o, float* rays_d,
+                                      float* target, void* stream) {
+    SSD_REQUIRE(store != nullptr && view_image != nullptr && c2w != nullptr && intr != nullptr, "sample_rays_u8: null input pointer");
+    SSD_REQUIRE(rays_o != nullptr && rays_d != nullptr && target != nullptr, "sample_rays_u8: null output pointer");
+    SSD_REQUIRE(S > 0 && V > 0 && R > 0, "sample_rays_u8: S, V and R must be positive (S = %u, V = %u, R = %u)", S, V, R);
+    SSD_REQUIRE(h > 0 && w > 0, "sample_rays_u8: an empty view (h = %u, w = %u)", h, w);
+    SSD_REQUIRE(num_images > 0, "sample_rays_u8: num_images == 0 (an empty store)");
+    SSD_REQUIRE(num_images <= 0x7fffffffull, "sample_rays_u8: %llu images, the int32 table reaches 2^31 - 1", (unsigned long long)num_images);
+    const uint64_t hw = (uint64_t)h * w, P = hw * V;
+    SSD_REQUIRE(hw < ((uint64_t)1 << 32) && P < ((uint64_t)1 << 32), "sample_rays_u8: V * h * w is 2^32 pixels per scene or more");
+    SSD_REQUIRE(inds != nullptr || R == P, "sample_rays_u8: inds == NULL takes every pixel, R must be V * h * w = %llu, got %u", (unsigned long long)P, R);
+    SSD_REQUIRE((((uintptr_t)rays_o | (uintptr_t)rays_d | (uintptr_t)target | (uintptr_t)view_image | (uintptr_t)c2w | (uintptr_t)intr) & 3u) == 0,
+                "sample_rays_u8: an output or a table is not 4-byte aligned");
+    SSD_REQUIRE(((uintptr_t)inds & 7u) == 0, "sample_rays_u8: inds is not 8-byte aligned");
+    const uint64_t total = (uint64_t)S * R;
+    SSD_REQUIRE(total <= ((uint64_t)1 << 38), "sample_rays_u8: S * R is more than 2^38 rays");
+    hipLaunchKernelGGL(k_sample_rays_u8, dim3((uint32_t)((total + RS_THREADS - 1) / RS_THREADS)), dim3(RS_THREADS), 0, (hipStream_t)stream, store, (uint32_t)hw, w,
+                       view_image, c2w, intr, V, inds, R, total, rays_o, rays_d, target);
+    SSD_CHECK_LAUNCH("sample_rays_u8");
     return SSDNERF_OK;
 }

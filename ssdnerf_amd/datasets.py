@@ -1,12 +1,14 @@
 """The reference's dataset (lib/datasets/shapenet_srn.py) and its loader, on a device-resident image store.
 
-Three layers:
+Four layers:
 
 ``ShapeNetSRN``   reads a folder tree in the SRN layout (``<prefix>/<scene>/{intrinsics.txt, rgb/*.png, pose/*.txt}``) with the reference's
                   constructor keywords and defaults; ``ds[i]`` is the reference's per-scene dict with CPU tensors (no GPU, no library).
 ``SceneStore``    every pixel of a dataset as ONE uint8 tensor (num_images, h, w, 3) -- on the GPU (``store='device'``) or in pinned host
                   memory (``store='host'``) -- and ``gather(image_indices)``: the fp32 views of a batch from one launch of
                   ``ssdnerf_gather_views_u8`` (csrc/scene_store.hip), bit-identical to the reference's ``img.astype(np.float32) / 255``.
+``StoredViews``   the conditioning views of a batch left IN the store (``build_dataloader(..., cond_imgs='stored')``): ``sample(inds)`` gives the
+                  rays and target colours of sampled pixels from one launch of ``ssdnerf_sample_rays_u8``, ``dense()`` the arrays themselves.
 ``SceneLoader``   an in-process iterable of batch dicts with exactly the keys ``train_step`` / ``val_step`` / ``evaluate_3d`` read, in the
                   reference's scene order (``parallel.shard_scenes`` for evaluation, lib/datasets/samplers/distributed_sampler.py for
                   training).  No worker processes and no per-iteration host traffic beyond a few hundred index bytes.
@@ -371,19 +373,19 @@ class SceneStore:
         self._staging: Optional[torch.Tensor] = None
         self._staging_free: Optional[torch.cuda.Event] = None
 
-    def _check_indices(self, image_indices) -> np.ndarray:
+    def _check_indices(self, image_indices, what: str = "SceneStore.gather") -> np.ndarray:
         if isinstance(image_indices, torch.Tensor):
             if image_indices.is_cuda:
-                raise ValueError("SceneStore.gather: the indices must be on the host (they are validated before they are uploaded)")
+                raise ValueError(f"{what}: the indices must be on the host (they are validated before they are uploaded)")
             image_indices = image_indices.numpy()
         idx = np.asarray(image_indices)
         if idx.ndim != 1 or idx.size == 0:
-            raise ValueError(f"SceneStore.gather: a non-empty 1-D list of image indices is needed, got shape {idx.shape}")
+            raise ValueError(f"{what}: a non-empty 1-D list of image indices is needed, got shape {idx.shape}")
         if idx.dtype.kind not in "iu":
-            raise ValueError(f"SceneStore.gather: integer indices are needed, got {idx.dtype}")
+            raise ValueError(f"{what}: integer indices are needed, got {idx.dtype}")
         if int(idx.min()) < 0 or int(idx.max()) >= self.num_images:
             bad = idx[(idx < 0) | (idx >= self.num_images)][0]
-            raise ValueError(f"SceneStore.gather: image index {int(bad)} is outside [0, {self.num_images})")
+            raise ValueError(f"{what}: image index {int(bad)} is outside [0, {self.num_images})")
         return idx.astype(np.int64)
 
     def gather(self, image_indices) -> torch.Tensor:
@@ -419,6 +421,78 @@ class SceneStore:
         return out
 
 
+class StoredViews:
+    """The conditioning views of a batch, left where they are: ``store`` (a device ``SceneStore``), the (S, V) table ``view_image`` of store image
+    numbers -- a HOST array, validated against the store before anything is uploaded -- and the views' cameras ``poses`` (S, V, 4, 4) /
+    ``intrinsics`` (S, V, 4) on the store's device.  It stands where the fp32 ``cond_imgs`` (S, V, h, w, 3) of a batch stands (``shape``,
+    ``size``, ``device``, ``dtype`` answer as that tensor would) and gives the fitting code what it reads from it:
+
+    ``sample(inds)``  (rays_o, rays_d, target), each (S, R, 3): pixels ``inds`` (S, R) int64 on the device -- or every pixel, ``None`` -- with
+                      their rays, from ONE launch of ``ssdnerf_sample_rays_u8`` (csrc/scene_store.hip), bit for bit what indexing the dense
+                      arrays gives.  An index outside [0, V*h*w) gives a NaN ray.
+    ``dense()``       (images, rays_o, rays_d), each (S, V, h, w, 3): the arrays themselves, by ``SceneStore.gather`` and ``nerf.get_cam_rays``,
+                      built on the first call and kept -- for consumers that need whole images.
+
+    ``sample_launches`` counts the calls of ``sample``; ``dense_calls`` the times the dense arrays were built (0 or 1)."""
+
+    dtype = torch.float32
+
+    def __init__(self, store: SceneStore, view_image, poses: torch.Tensor, intrinsics: torch.Tensor):
+        if not isinstance(store, SceneStore) or store.store != "device":
+            raise ValueError("StoredViews: a SceneStore with store='device' is needed (sampling from the pinned host store is not implemented)")
+        if isinstance(view_image, torch.Tensor):
+            if view_image.is_cuda:
+                raise ValueError("StoredViews: view_image must be on the host (it is validated before it is uploaded)")
+            view_image = view_image.numpy()
+        table = np.asarray(view_image)
+        if table.ndim != 2:
+            raise ValueError(f"StoredViews: view_image must be (scenes, views), got shape {table.shape}")
+        self.view_image = store._check_indices(table.reshape(-1), "StoredViews").reshape(table.shape)
+        S, V = self.view_image.shape
+        h, w = store.shape[1:3]
+        if V * h * w >= 1 << 32:
+            raise ValueError(f"StoredViews: {V} views of {h} x {w} are 2^32 pixels per scene or more")
+        if tuple(poses.shape) != (S, V, 4, 4) or tuple(intrinsics.shape) != (S, V, 4):
+            raise ValueError(f"StoredViews: poses {tuple(poses.shape)} / intrinsics {tuple(intrinsics.shape)} do not fit a ({S}, {V}) view table")
+        self.store = store
+        self.poses = poses.detach().to(device=store.device, dtype=torch.float32).contiguous()
+        self.intrinsics = intrinsics.detach().to(device=store.device, dtype=torch.float32).contiguous()
+        self.device = self.poses.device
+        self.view_image_dev = torch.from_numpy(self.view_image.astype(np.int32)).to(self.device)
+        self.shape = torch.Size((S, V, h, w, 3))
+        self.sample_launches = self.dense_calls = 0
+        self._dense: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None
+
+    def size(self, dim: Optional[int] = None):
+        return self.shape if dim is None else self.shape[dim]
+
+    def sample(self, inds: Optional[torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        from . import _cabi as C
+        S, V, h, w, _ = self.shape
+        if inds is None:
+            R = V * h * w
+        else:
+            if inds.dtype != torch.int64 or inds.dim() != 2 or inds.size(0) != S or inds.device != self.poses.device:
+                raise ValueError(f"StoredViews.sample: inds must be int64 ({S}, R) on {self.device}, got {inds.dtype} {tuple(inds.shape)} on {inds.device}")
+            inds, R = inds.contiguous(), inds.size(1)
+        with torch.cuda.device(self.device):
+            rays_o, rays_d, target = (torch.empty((S, R, 3), dtype=torch.float32, device=self.device) for _ in range(3))
+            C.check(C.lib().ssdnerf_sample_rays_u8(C.ptr(self.store.pixels), self.store.num_images, h, w, C.ptr(self.view_image_dev), C.ptr(self.poses),
+                                                   C.ptr(self.intrinsics), S, V, C.ptr(inds), R, C.ptr(rays_o), C.ptr(rays_d), C.ptr(target),
+                                                   C.stream()), "sample_rays_u8")
+        self.sample_launches += 1
+        return rays_o, rays_d, target
+
+    def dense(self) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        if self._dense is None:
+            from . import nerf
+            images = self.store.gather(self.view_image.reshape(-1)).view(self.shape)
+            rays_o, rays_d = nerf.get_cam_rays(self.poses, self.intrinsics, self.shape[2], self.shape[3])
+            self._dense = (images, rays_o, rays_d)
+            self.dense_calls += 1
+        return self._dense
+
+
 # ---------------------------------------------------------------------------------------------- the loader
 def _wrap_pad(indices: List[int], length: int) -> List[int]:
     """the list padded to ``length`` with its own front (the sampler's `indices += indices[:total - len]`; repeated when one wrap is not enough)"""
@@ -433,9 +507,13 @@ class SceneLoader:
     scene ids of an epoch, pure Python; iterating cuts it into batches of ``samples_per_gpu`` and fills each from the ``SceneStore``."""
 
     def __init__(self, dataset: ShapeNetSRN, samples_per_gpu: int, shuffle: bool = False, split_data: bool = False, seed: int = 0,
-                 rank: Optional[int] = None, world_size: Optional[int] = None, store: str = "device", device=None):
+                 rank: Optional[int] = None, world_size: Optional[int] = None, store: str = "device", device=None, cond_imgs: str = "dense"):
         if samples_per_gpu < 1:
             raise ValueError(f"samples_per_gpu must be at least 1, got {samples_per_gpu}")
+        if cond_imgs not in ("dense", "stored"):
+            raise ValueError(f"cond_imgs must be 'dense' or 'stored', got {cond_imgs!r}")
+        if cond_imgs == "stored" and store != "device":
+            raise ValueError(f"cond_imgs='stored' samples rays from the device store; store={store!r} keeps the pixels in host memory")
         if rank is None or world_size is None:
             import torch.distributed as dist
             on = dist.is_available() and dist.is_initialized()
@@ -444,7 +522,7 @@ class SceneLoader:
         if not 0 <= rank < world_size:
             raise ValueError(f"rank {rank} is outside [0, {world_size})")
         self.dataset, self.samples_per_gpu, self.shuffle, self.split_data, self.seed = dataset, int(samples_per_gpu), shuffle, split_data, seed
-        self.rank, self.world_size, self.store_kind, self.device = rank, world_size, store, device
+        self.rank, self.world_size, self.store_kind, self.device, self.cond_imgs = rank, world_size, store, device, cond_imgs
         self.epoch = 0
         self._store: Optional[SceneStore] = None
         self._dev: Optional[Dict[str, torch.Tensor]] = None
@@ -506,7 +584,10 @@ class SceneLoader:
             scene_where = torch.tensor(out["scene_id"], dtype=torch.int64).to(dev["poses"].device)
             out[key + "_intrinsics"] = dev["intrinsics"][scene_where][:, None].expand(S, V, 4).contiguous()
             out[key + "_img_paths"] = [r[key + "_img_paths"] for r in recs]
-            if ds.load_imgs:
+            if ds.load_imgs and key == "cond" and self.cond_imgs == "stored":       # the views stay in the store: no launch here
+                out[key + "_imgs"] = StoredViews(self.scene_store, np.asarray(flat, dtype=np.int64).reshape(S, V), out[key + "_poses"],
+                                                 out[key + "_intrinsics"])
+            elif ds.load_imgs:
                 out[key + "_imgs"] = self.scene_store.gather(flat).view(S, V, *self.scene_store.shape[1:])   # ONE launch per view group
         if all("code" in r for r in recs):
             out["code"] = [r["code"] for r in recs]
@@ -529,8 +610,10 @@ def build_dataset(cfg, default_args=None) -> ShapeNetSRN:
     return DATASETS.build(_plain(cfg), default_args)
 
 
-def build_dataloader(dataset, samples_per_gpu, shuffle=False, split_data=False, seed=0, rank=None, world_size=None, store="device", device=None) -> SceneLoader:
+def build_dataloader(dataset, samples_per_gpu, shuffle=False, split_data=False, seed=0, rank=None, world_size=None, store="device", device=None,
+                     cond_imgs="dense") -> SceneLoader:
     """The loader of one rank.  ``shuffle=False`` (evaluation): this rank's ``parallel.shard_scenes`` range in order, ragged last batch, no padding.
-    ``shuffle=True`` (training): the reference sampler's order (lib/datasets/samplers/distributed_sampler.py)."""
+    ``shuffle=True`` (training): the reference sampler's order (lib/datasets/samplers/distributed_sampler.py).
+    ``cond_imgs='stored'``: the batches' ``cond_imgs`` is a ``StoredViews`` handle instead of the fp32 tensor."""
     return SceneLoader(dataset, samples_per_gpu, shuffle=shuffle, split_data=split_data, seed=seed, rank=rank, world_size=world_size, store=store,
-                       device=device)
+                       device=device, cond_imgs=cond_imgs)

@@ -5,9 +5,9 @@ base_nerf.py:231-316, 403-492 and diffusion_nerf.py:241-404; SURVEY.md section 8
 The reference spreads this over nested closures and long method bodies; here it is four small objects that the model classes compose:
 
   Conditioning      the observations of a batch of scenes: images, their rays (generated on the device by one HIP pass) and the per-scene
-                    cone angle ``dt_gamma``;
+                    cone angle ``dt_gamma`` -- or, store-backed, a ``datasets.StoredViews`` handle in place of the three arrays;
   RayBatcher        which pixels each step looks at: disjoint chunks of one random permutation per scene, cycled (or everything, when the
-                    views are small), gathered on the device;
+                    views are small), gathered on the device -- from the arrays, or by one launch straight from the uint8 image store;
   CodeFitter        N rendering-loss iterations on pre-activation code leaves: activation -> (periodic) density refresh -> train-branch
                     render + loss -> backward on top of an optional seed gradient (the diffusion prior's) -> optimizer / scheduler step;
   GuidanceObjective the ``grad_guide_fn`` of rendering-guided DDIM as an object that owns its density grid and step counter.
@@ -17,60 +17,102 @@ The model passes ITSELF in: ``loss`` / ``update_extra_state`` are looked up on i
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
 from typing import Dict, Iterator, List, Optional, Sequence, Union
 
 import torch
 
 from . import nerf
+from .datasets import StoredViews
 from .optim import step_all
 
 
-@dataclass
 class Conditioning:
-    images: torch.Tensor        # (S, V, h, w, 3)
-    rays_o: torch.Tensor        # (S, V, h, w, 3)
-    rays_d: torch.Tensor
-    dt_gamma: torch.Tensor      # (S,) cone angle of the march: dt_gamma_scale / mean focal length
+    """``Conditioning(images, rays_o, rays_d, dt_gamma)``: three (S, V, h, w, 3) arrays and the (S,) cone angle of the march,
+    dt_gamma_scale / mean focal length.  Store-backed: ``images`` is a ``datasets.StoredViews`` and ``rays_o = rays_d = None``; ``stored`` is
+    then that handle, ``RayBatcher`` samples from it, and ``images`` / ``rays_o`` / ``rays_d`` are its ``dense()`` arrays, built when first read."""
+
+    def __init__(self, images, rays_o: Optional[torch.Tensor], rays_d: Optional[torch.Tensor], dt_gamma):
+        self.stored: Optional[StoredViews] = images if isinstance(images, StoredViews) else None
+        if self.stored is not None and (rays_o is not None or rays_d is not None):
+            raise ValueError("Conditioning: a StoredViews handle makes its own rays; pass rays_o = rays_d = None with it")
+        self._arrays = (images, rays_o, rays_d)
+        self.dt_gamma = dt_gamma
 
     @classmethod
     def from_batch(cls, data: Dict, dt_gamma_scale: float) -> "Conditioning":
         imgs, intr, poses = data["cond_imgs"], data["cond_intrinsics"], data["cond_poses"]
+        if isinstance(imgs, StoredViews):                                # nothing per pixel happens here
+            return cls(imgs, None, None, dt_gamma_scale / imgs.intrinsics[..., :2].mean(dim=(-2, -1)))
         h, w = imgs.shape[2:4]
         o, d = nerf.get_cam_rays(poses, intr, h, w)
         return cls(imgs, o, d, dt_gamma_scale / intr[..., :2].mean(dim=(-2, -1)))
 
+    def _array(self, i: int) -> torch.Tensor:
+        return self._arrays[i] if self.stored is None else self.stored.dense()[i]
+
+    @property
+    def images(self) -> torch.Tensor:
+        return self._array(0)
+
+    @property
+    def rays_o(self) -> torch.Tensor:
+        return self._array(1)
+
+    @property
+    def rays_d(self) -> torch.Tensor:
+        return self._array(2)
+
+    def ray_args(self):
+        """(cond_imgs, cond_rays_o, cond_rays_d) as ``BaseNeRF.inverse_code`` / ``loss_decoder`` / ``ray_sample`` take them: the arrays, or
+        (handle, None, None) -- handing these on never builds the dense arrays"""
+        return self._arrays
+
+    @property
+    def device(self) -> torch.device:
+        return self._arrays[0].device
+
     @property
     def num_scenes(self) -> int:
-        return self.images.size(0)
+        return self._arrays[0].size(0)
 
     @property
     def pixels_per_scene(self) -> int:
-        return self.images.shape[1:4].numel()
+        return self._arrays[0].shape[1:4].numel()
 
 
 class RayBatcher:
     """``batch(k)`` -> (rays_o, rays_d, target), each (S, R, 3).  With more pixels than ``rays_per_step`` the pixels of every scene are
     permuted once and step k takes chunk k mod n_chunks (``fixed=True``: base_nerf.py:263-274, used by inversion and guidance), or a fresh
-    random subset is drawn per call (``fixed=False``: base_nerf.py:231-261 without indices, used by ``loss_decoder``)."""
+    random subset is drawn per call (``fixed=False``: base_nerf.py:231-261 without indices, used by ``loss_decoder``).  On a store-backed
+    ``Conditioning`` the indices are drawn by the same calls in the same order and the gather is ``StoredViews.sample``: one launch per batch."""
 
     def __init__(self, cond: Conditioning, rays_per_step: int, fixed: bool = True):
         self.S, self.P, self.R = cond.num_scenes, cond.pixels_per_scene, rays_per_step
-        self.flat = (cond.rays_o.reshape(self.S, self.P, 3), cond.rays_d.reshape(self.S, self.P, 3), cond.images.reshape(self.S, self.P, 3))
+        self.stored, self.device = cond.stored, cond.device
+        self.flat = None
+        if self.stored is None:
+            self.flat = (cond.rays_o.reshape(self.S, self.P, 3), cond.rays_d.reshape(self.S, self.P, 3), cond.images.reshape(self.S, self.P, 3))
         self.chunks: Optional[Sequence[torch.Tensor]] = None
         if fixed and self.P > self.R:
-            dev = cond.images.device
-            self.chunks = torch.stack([torch.randperm(self.P, device=dev) for _ in range(self.S)], dim=0).split(self.R, dim=1)
+            perms = torch.stack([torch.randperm(self.P, device=self.device) for _ in range(self.S)], dim=0)
+            if self.stored is None:
+                self.chunks = perms.split(self.R, dim=1)
+            else:       # the same chunks, each (S, R) contiguous as the kernel reads them: one reordering copy here, none per batch
+                whole = self.P // self.R
+                self.chunks = tuple(perms[:, :whole * self.R].reshape(self.S, whole, self.R).transpose(0, 1).contiguous())
+                if whole * self.R < self.P:
+                    self.chunks += (perms[:, whole * self.R:].contiguous(),)
 
     def indices(self, k: int) -> Optional[torch.Tensor]:
         return None if self.chunks is None else self.chunks[k % len(self.chunks)]
 
     def take(self, inds: Optional[torch.Tensor]):
         if self.P <= self.R:
-            return self.flat
+            return self.flat if self.stored is None else self.stored.sample(None)
         if inds is None:
-            dev = self.flat[0].device
-            inds = torch.stack([torch.randperm(self.P, device=dev)[:self.R] for _ in range(self.S)], dim=0)
+            inds = torch.stack([torch.randperm(self.P, device=self.device)[:self.R] for _ in range(self.S)], dim=0)
+        if self.stored is not None:
+            return self.stored.sample(inds)
         rows = torch.arange(self.S, device=inds.device)[:, None]
         return tuple(t[rows, inds] for t in self.flat)
 
@@ -155,7 +197,7 @@ class GuidanceObjective:
 
     def __init__(self, model, decoder, cond: Conditioning, cfg: Dict, march_noises=None, density_jitters=None):
         self.model, self.decoder, self.cond, self.cfg = model, decoder, cond, cfg
-        dev, S, H3 = cond.images.device, cond.num_scenes, model.grid_size ** 3
+        dev, S, H3 = cond.device, cond.num_scenes, model.grid_size ** 3
         self.grid = torch.zeros((S, H3), device=dev)                                   # fp32 here, as in the reference (diffusion_nerf.py:278)
         self.bits = torch.zeros((S, H3 // 8), dtype=torch.uint8, device=dev)
         self.batcher = RayBatcher(cond, cfg.get("n_inverse_rays", 4096), fixed=True)

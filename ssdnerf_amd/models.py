@@ -28,6 +28,7 @@ from . import nerf
 from .codes import attr_path_get, attr_path_set, frozen
 from .codes import IdentityCode, MSELoss, NormalizedTanhCode, RegLoss, TanhCode, TVLoss  # noqa: F401  (registered here for config builds)
 from .density import get_density as _get_density, update_density_grid
+from .datasets import StoredViews
 from .fitting import CodeFitter, Conditioning, GuidanceObjective, RayBatcher
 from .metrics import image_metrics
 from .optim import HIPAdam, step_all
@@ -207,12 +208,14 @@ class BaseNeRF(nn.Module):
     # ---- rendering loss -------------------------------------------------------------------------------------------------------------------------
     @staticmethod
     def ray_sample(cond_rays_o, cond_rays_d, cond_imgs, n_samples, sample_inds=None):
-        """(S, n_samples, 3) rays and target colours out of the (S, V, h, w, 3) arrays: the given pixel indices, or a fresh random subset."""
+        """(S, n_samples, 3) rays and target colours out of the (S, V, h, w, 3) arrays: the given pixel indices, or a fresh random subset.
+        ``cond_imgs`` may be a ``datasets.StoredViews`` (``cond_rays_o = cond_rays_d = None``): one launch on the uint8 store instead."""
         return RayBatcher(Conditioning(cond_imgs, cond_rays_o, cond_rays_d, None), n_samples, fixed=False).take(sample_inds)
 
     @staticmethod
     def get_raybatch_inds(cond_imgs, n_inverse_rays):
-        chunks = RayBatcher(Conditioning(cond_imgs, cond_imgs, cond_imgs, None), n_inverse_rays, fixed=True).chunks
+        stand_in = None if isinstance(cond_imgs, StoredViews) else cond_imgs
+        chunks = RayBatcher(Conditioning(cond_imgs, stand_in, stand_in, None), n_inverse_rays, fixed=True).chunks
         return (None, None) if chunks is None else (chunks, len(chunks))
 
     def loss(self, decoder, code, density_bitfield, target_rgbs, rays_o, rays_d, dt_gamma=0.0, return_decoder_loss=False,
@@ -233,13 +236,14 @@ class BaseNeRF(nn.Module):
 
     def loss_decoder(self, decoder, code, density_bitfield, cond_rays_o, cond_rays_d, cond_imgs, dt_gamma=0.0, cfg=dict(), **kwargs):
         """Rendering loss on ``n_decoder_rays`` freshly drawn rays through the TRAIN branch, decoder regulariser included; the logged parts are
-        detached 0-dim tensors (the reference turns each into a Python float: one device sync per entry)."""
+        detached 0-dim tensors (the reference turns each into a Python float: one device sync per entry).  ``cond_imgs`` may be a
+        ``datasets.StoredViews`` with ``cond_rays_o = cond_rays_d = None``."""
         was_training = decoder.training
         decoder.train(True)
         try:
             rays_o, rays_d, target = self.ray_sample(cond_rays_o, cond_rays_d, cond_imgs, n_samples=cfg.get("n_decoder_rays", 4096))
             rgb, total, parts = self.loss(decoder, code, density_bitfield, target, rays_o, rays_d, dt_gamma, return_decoder_loss=True,
-                                          scale_num_ray=cond_rays_o.shape[1:4].numel(), cfg=cfg, **kwargs)
+                                          scale_num_ray=(cond_imgs if cond_rays_o is None else cond_rays_o).shape[1:4].numel(), cfg=cfg, **kwargs)
         finally:
             decoder.train(was_training)
         return total, {k: v.detach() for k, v in parts.items()}, rgb, target
@@ -250,7 +254,8 @@ class BaseNeRF(nn.Module):
                      march_noises=None, density_jitters=None):
         """``cfg['n_inverse_steps']`` rendering-loss iterations on ``code_`` in place (``fitting.CodeFitter``), the decoder frozen; missing state
         (codes, grid, bitfield, optimizer, scheduler) is created.  ``prior_grad`` seeds every iteration's gradient.  ``march_noises`` /
-        ``density_jitters`` (extra): injected draws, consumed in order.
+        ``density_jitters`` (extra): injected draws, consumed in order.  ``cond_imgs`` may be a ``datasets.StoredViews`` with ``cond_rays_o =
+        cond_rays_d = None``: the ray batches then come straight from the uint8 image store.
         -> (activated code, density_grid, density_bitfield, last loss, its parts, last rendered rgb, its targets)"""
         dev = get_module_device(self)
         S = cond_imgs.size(0)
@@ -323,7 +328,7 @@ class BaseNeRF(nn.Module):
         else:
             cond = Conditioning.from_batch(data, self.test_cfg.get("dt_gamma_scale", 0.0))
             with torch.enable_grad():
-                code, grid, bits, _, _, rgb, target = self.inverse_code(decoder, cond.images, cond.rays_o, cond.rays_d, dt_gamma=cond.dt_gamma,
+                code, grid, bits, _, _, rgb, target = self.inverse_code(decoder, *cond.ray_args(), dt_gamma=cond.dt_gamma,
                                                                         cfg=self.test_cfg, march_noises=march_noises, density_jitters=density_jitters)
         with torch.no_grad():
             log_vars, pred, extra = self._eval_test_views(data, decoder, code, bits)
@@ -443,7 +448,8 @@ class MultiSceneNeRF(BaseNeRF):
         seed gradients), step decoder and codes, write the cache back, log"""
         cfg = self.train_cfg
         self.update_extra_state(decoder, code.detach(), density_grid, density_bitfield, 0, density_thresh=cfg.get("density_thresh", 0.01))
-        loss, parts, rgb, target = self.loss_decoder(decoder, code, density_bitfield, cond.rays_o, cond.rays_d, cond.images, cond.dt_gamma, cfg=cfg)
+        imgs, rays_o, rays_d = cond.ray_args()
+        loss, parts, rgb, target = self.loss_decoder(decoder, code, density_bitfield, rays_o, rays_d, imgs, cond.dt_gamma, cfg=cfg)
         log_vars.update(parts)
         if seed_grads is not None:
             for leaf, g in zip(leaves, seed_grads):
@@ -465,7 +471,7 @@ class MultiSceneNeRF(BaseNeRF):
         cond = self._conditioning(data, cfg)
         extra = cfg.get("extra_scene_step", 0)
         if extra > 0:
-            self.inverse_code(self.decoder, cond.images, cond.rays_o, cond.rays_d, dt_gamma=cond.dt_gamma, cfg=dict(cfg, n_inverse_steps=extra),
+            self.inverse_code(self.decoder, *cond.ray_args(), dt_gamma=cond.dt_gamma, cfg=dict(cfg, n_inverse_steps=extra),
                               code_=leaves, density_grid=grid, density_bitfield=bits, code_optimizer=code_optimizers)
         for opt in (*code_optimizers, optimizer["decoder"]):
             opt.zero_grad()
@@ -554,7 +560,7 @@ class DiffusionNeRF(MultiSceneNeRF):
         if extra > 0:
             assert code_optimizers
             seeds = [leaf.grad.detach().clone() for leaf in leaves]
-            _, _, _, _, parts, _, _ = self.inverse_code(decoder, cond.images, cond.rays_o, cond.rays_d, dt_gamma=cond.dt_gamma,
+            _, _, _, _, parts, _, _ = self.inverse_code(decoder, *cond.ray_args(), dt_gamma=cond.dt_gamma,
                                                         cfg=dict(cfg, n_inverse_steps=extra), code_=leaves, density_grid=grid, density_bitfield=bits,
                                                         code_optimizer=code_optimizers, prior_grad=seeds)
             log_vars.update({k: v.detach() for k, v in parts.items()})
@@ -640,7 +646,7 @@ class DiffusionNeRF(MultiSceneNeRF):
         cfg = self.test_cfg
         diffusion, decoder = self._eval_diffusion(), self._modules_for_eval()
         cond = self._conditioning(data, cfg)
-        dev, S = cond.images.device, cond.num_scenes
+        dev, S = cond.device, cond.num_scenes
         extra, n_outer = cfg.get("extra_scene_step", 0), cfg.get("n_inverse_steps", 100)
         assert n_outer > 0
         march_noises = None if march_noises is None else iter(march_noises)
@@ -681,7 +687,7 @@ class DiffusionNeRF(MultiSceneNeRF):
                         next_noise = _host_noise(x0_in.detach())
                         rng_after_prefetch = torch.get_rng_state()
                     if extra > 0:
-                        self.inverse_code(decoder, cond.images, cond.rays_o, cond.rays_d, dt_gamma=cond.dt_gamma, cfg=inner_cfg, code_=code_,
+                        self.inverse_code(decoder, *cond.ray_args(), dt_gamma=cond.dt_gamma, cfg=inner_cfg, code_=code_,
                                           density_grid=density_grid, density_bitfield=density_bitfield, code_optimizer=opt, code_scheduler=sch,
                                           prior_grad=code_.grad.detach().clone(), march_noises=march_noises, density_jitters=density_jitters)
                         continue
@@ -689,8 +695,9 @@ class DiffusionNeRF(MultiSceneNeRF):
                     if march_noises is not None:
                         decoder.injected_noises = next(march_noises)
                     try:
-                        fit_loss, _, _, _ = self.loss_decoder(decoder, self.code_activation(code_), density_bitfield, cond.rays_o, cond.rays_d,
-                                                              cond.images, cond.dt_gamma, cfg=cfg)
+                        imgs, rays_o, rays_d = cond.ray_args()
+                        fit_loss, _, _, _ = self.loss_decoder(decoder, self.code_activation(code_), density_bitfield, rays_o, rays_d, imgs,
+                                                              cond.dt_gamma, cfg=cfg)
                     finally:
                         decoder.injected_noises = None
                     fit_loss.backward()
