@@ -397,6 +397,50 @@ int ssdnerf_sample_rays_u8(const uint8_t* store, uint64_t num_images, uint32_t h
                            const float* intr, uint32_t S, uint32_t V, const int64_t* inds, uint32_t R, float* rays_o, float* rays_d, float* target,
                            void* stream);
 
+/* The per-scene training cache ON THE DEVICE (csrc/scene_cache.hip, conversions in csrc/cache_cvt.h; scene_cache.DeviceSceneCache): what
+ * MultiSceneNeRF.load_cache / save_cache move per training step -- a scene's pre-activation code, the two Adam moments of its optimizer, its
+ * density grid and bitfield -- between a store of `slots` scenes and the batch buffers of a step, a whole batch in ONE launch each way.
+ *   store (ssdnerf_cache_store, a HOST struct read before the call returns; its arrays are on the device):
+ *     code [slots][numel]            code_dtype:   0 = fp32 | 1 = fp16
+ *     exp_avg, exp_avg_sq [slots][numel]  moment_dtype: 0 = fp32 | 2 = bf16     the pairs (0, 0) and (1, 2) exist, nothing else
+ *     density_grid [slots][grid_bytes], density_bitfield [slots][bits_bytes]      bytes (the grid is fp16, which these calls never interpret)
+ *   rows: a HOST array of S <= SSDNERF_CACHE_MAX_SCENES entries {slot, row, has_state} that travels in the kernel arguments (longer batches
+ *     take several calls); batch buffers of S rows: leaves, m, v fp32 [S][numel], grid [S][grid_bytes], bits [S][bits_bytes].
+ * ssdnerf_cache_load_multi, per entry: leaves[row] <- code[slot] widened to fp32 (exact); with has_state m[row] <- exp_avg[slot] and v[row] <-
+ *   exp_avg_sq[slot] widened, without it those two rows are left untouched; grid[row], bits[row] <- the slot's bytes.  A slot may be named twice,
+ *   a batch row may not.
+ * ssdnerf_cache_store_multi, per entry, the reverse: with a 16-bit target every value is clamped to the target's finite range and then rounded
+ *   to nearest even -- bit for bit torch's `x.clamp(finfo.min, finfo.max).to(dtype)`: +-Inf becomes +-max, the sign of zero and subnormals are
+ *   kept (fp16 subnormals are produced), NaN stays NaN (payload unspecified); with an fp32 target it is a bit copy, no clamp.  Without has_state
+ *   the slot's two moment rows are left untouched.  A slot may not be named twice.
+ * m and v may be NULL when no entry has has_state set.  A block owns a chunk of one entry's work, the grid is the concatenation over all
+ * entries; 16-byte accesses where both sides of a row are 16-byte aligned, element by element otherwise (any numel, grid_bytes, bits_bytes).
+ * Nothing outside the named slots (store) / batch rows (load) is written.  No device table, no allocation, no host synchronisation, no
+ * workspace.  A null pointer, S == 0 or > SSDNERF_CACHE_MAX_SCENES, slots == 0, a slot >= slots, a row >= S, a has_state other than 0 / 1, a dtype
+ * pair other than the two above, numel, grid_bytes or bits_bytes == 0 or > 2^40, an fp32 array that is not 4-byte or a 16-bit array that is not
+ * 2-byte aligned, a slot twice (store) and a row twice (load) fail with SSDNERF_E_INVALID before any HIP call. */
+#define SSDNERF_CACHE_MAX_SCENES 32
+typedef struct ssdnerf_cache_store {
+    void* code;
+    void* exp_avg;
+    void* exp_avg_sq;
+    void* density_grid;
+    void* density_bitfield;
+    uint64_t slots, numel, grid_bytes, bits_bytes;
+    int32_t code_dtype, moment_dtype;
+} ssdnerf_cache_store;
+typedef struct ssdnerf_cache_row {
+    uint32_t slot;      /* scene of the store */
+    uint32_t row;       /* row of the batch buffers */
+    uint32_t has_state; /* 1: the moments travel too */
+    uint32_t reserved;  /* pads the entry to 16 bytes */
+} ssdnerf_cache_row;
+uint32_t ssdnerf_cache_max_scenes(void);
+int ssdnerf_cache_load_multi(const ssdnerf_cache_store* store, const ssdnerf_cache_row* rows, uint32_t S, float* leaves, float* m, float* v,
+                             void* grid, void* bits, void* stream);
+int ssdnerf_cache_store_multi(const ssdnerf_cache_store* store, const ssdnerf_cache_row* rows, uint32_t S, const float* leaves, const float* m,
+                              const float* v, const void* grid, const void* bits, void* stream);
+
 /* ---- Part 3: denoising-UNet glue (lib/models/architecture/ddpm/modules.py:12-129, denoising.py:178-187) ------------------
  * Activations are channel-last: x, y are [B][HW][C] of dtype 0 = fp32, 1 = fp16, 2 = bf16.
  *

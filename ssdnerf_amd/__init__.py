@@ -9,4 +9,5 @@ from . import registry  # noqa: F401
 from . import decoders, diffusion, models, unet  # noqa: F401  (register module types)
 from . import fidkid  # noqa: F401  (registers the FIDKID metric)
 from . import ema  # noqa: F401  (registers ExponentialMovingAverageHook)
+from .scene_cache import DeviceSceneCache  # noqa: F401  (MultiSceneNeRF(cache_store='device'))
 from .registry import HOOKS, METRICS, MODELS, MODULES, build_hook, build_module  # noqa: F401

@@ -37,6 +37,7 @@ EXPORTS = [
     "ssdnerf_adam_max_tensors", "ssdnerf_adam_step_multi",
     "ssdnerf_gather_views_u8", "ssdnerf_sample_rays_u8",
     "ssdnerf_ema_chunk", "ssdnerf_ema_plan_build", "ssdnerf_ema_update_multi",
+    "ssdnerf_cache_max_scenes", "ssdnerf_cache_load_multi", "ssdnerf_cache_store_multi",
 ]
 
 
@@ -51,6 +52,18 @@ class EmaRow(ctypes.Structure):
     """``ssdnerf_ema_row`` (include/ssdnerf_hip.h): one (source, EMA) tensor pair of the plan ``ssdnerf_ema_update_multi`` launches over"""
     _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("numel", ctypes.c_uint64), ("trainable", ctypes.c_uint32),
                 ("first_block", ctypes.c_uint32)]
+
+
+class CacheStore(ctypes.Structure):
+    """``ssdnerf_cache_store`` (include/ssdnerf_hip.h): the five device arrays of the scene cache, their sizes and dtype codes (0 fp32, 1 fp16, 2 bf16)"""
+    _fields_ = [("code", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p), ("exp_avg_sq", ctypes.c_void_p), ("density_grid", ctypes.c_void_p),
+                ("density_bitfield", ctypes.c_void_p), ("slots", ctypes.c_uint64), ("numel", ctypes.c_uint64), ("grid_bytes", ctypes.c_uint64),
+                ("bits_bytes", ctypes.c_uint64), ("code_dtype", ctypes.c_int32), ("moment_dtype", ctypes.c_int32)]
+
+
+class CacheRow(ctypes.Structure):
+    """``ssdnerf_cache_row`` (include/ssdnerf_hip.h): one (slot, batch row, has_state) entry of ``ssdnerf_cache_load_multi`` / ``_store_multi``"""
+    _fields_ = [("slot", ctypes.c_uint32), ("row", ctypes.c_uint32), ("has_state", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
 def lib_path() -> str:
@@ -107,6 +120,10 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_ema_chunk.argtypes = []
         l.ssdnerf_ema_plan_build.argtypes = [ctypes.POINTER(EmaRow), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]
         l.ssdnerf_ema_update_multi.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_float, ctypes.c_float, ctypes.c_void_p]
+        l.ssdnerf_cache_max_scenes.restype = ctypes.c_uint32
+        l.ssdnerf_cache_max_scenes.argtypes = []
+        for fn in (l.ssdnerf_cache_load_multi, l.ssdnerf_cache_store_multi):
+            fn.argtypes = [ctypes.POINTER(CacheStore), ctypes.POINTER(CacheRow), ctypes.c_uint32] + [ctypes.c_void_p] * 6
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -346,17 +346,29 @@ class BaseNeRF(nn.Module):
 @MODELS.register_module()
 class MultiSceneNeRF(BaseNeRF):
     """+ the per-scene cache of pre-activation codes and optimizer states (wire format and 16-bit casting rules: ``scene_cache.py``).  The RAM
-    cache is sharded over ranks with the ``round(linspace)`` split of the scene sampler, so a rank only holds the scenes it is handed."""
+    cache is sharded over ranks with the ``round(linspace)`` split of the scene sampler, so a rank only holds the scenes it is handed.
+    ``cache_store='host'`` (the default) keeps it as a dict of CPU tensors; ``'device'`` keeps the same shard in device arrays
+    (``scene_cache.DeviceSceneCache``: ``load_cache`` / ``save_cache`` are one HIP launch each, no host round trip; Adam-shaped optimizer states
+    only; needs ``cache_size > 0`` and a model on the GPU)."""
 
-    def __init__(self, *args, cache_size=0, cache_16bit=False, num_file_writers=0, **kwargs):
+    def __init__(self, *args, cache_size=0, cache_16bit=False, num_file_writers=0, cache_store="host", **kwargs):
         super().__init__(*args, **kwargs)
         self.cache_size, self.cache_16bit, self.num_file_writers = cache_size, cache_16bit, num_file_writers
         self.cache, self.cache_loaded, self.file_writers = None, False, None
+        if cache_store not in ("host", "device"):
+            raise ValueError(f"cache_store={cache_store!r}: 'host' or 'device'")
+        if cache_store == "device" and not cache_size > 0:
+            raise ValueError("cache_store='device' needs cache_size > 0 (the device cache holds one slot per scene)")
+        self.cache_store = cache_store
         if cache_size > 0:
             import torch.distributed as dist
             from .parallel import shard_scenes
             rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_available() and dist.is_initialized() else (0, 1)
-            self.cache = dict.fromkeys(shard_scenes(cache_size, rank, world))
+            if cache_store == "device":
+                from .scene_cache import DeviceSceneCache
+                self.cache = DeviceSceneCache(shard_scenes(cache_size, rank, world), self.code_size, self.grid_size, cache_16bit)
+            else:
+                self.cache = dict.fromkeys(shard_scenes(cache_size, rank, world))
 
     def _cached_entries(self, data) -> List[Optional[Dict]]:
         if self.cache is None:
@@ -376,6 +388,8 @@ class MultiSceneNeRF(BaseNeRF):
         ``data['scene_id']``: RAM cache (filled once from ``train_cfg['cache_load_from']``) > ``data['code']`` > fresh."""
         from .scene_cache import optimizer_set_state
         dev = get_module_device(self)
+        if self.cache_store == "device":
+            return self._load_cache_device(data, dev)
         entries = self._cached_entries(data)
         leaves, grids, bits = [], [], []
         for entry in entries:
@@ -403,6 +417,8 @@ class MultiSceneNeRF(BaseNeRF):
         """Scenes back into the RAM cache (in place where an entry exists) and, with ``train_cfg['save_dir']``, to ``<save_dir>/<name>.pth``
         (fp16 codes + bf16 optimizer moments under ``cache_16bit``).  Tensors handed to the writer threads are private copies."""
         from .scene_cache import _FileWriters, load_tensor_to_dict, optimizer_state_copy, optimizer_state_to, out_dict_to
+        if self.cache_store == "device":
+            return self._save_cache_device(code_list_, code_optimizers, density_grid, density_bitfield, scene_id, scene_name)
         code_dtype, state_dtype = code_list_[0].dtype, torch.float32
         if self.cache_16bit:
             code_dtype, state_dtype = (torch.float16 if code_dtype == torch.float32 else code_dtype), torch.bfloat16
@@ -438,6 +454,71 @@ class MultiSceneNeRF(BaseNeRF):
                     self.file_writers.put(i, record)
                 else:
                     torch.save(record, os.path.join(save_dir, scene_name[i] + ".pth"))
+
+    # ---- cache_store='device': the same two calls on scene_cache.DeviceSceneCache, one launch each --------------------------------------------
+    def _load_cache_device(self, data, dev):
+        """``load_cache`` out of the device cache: every filled slot of the batch arrives in fp32 batch buffers by ONE launch -- its leaf is a row
+        of the leaf buffer, its optimizer's moments rows of the two moment buffers; fresh scenes are initialised per entry, in batch order (the
+        host path's random stream).  A batch without fresh scenes returns the grid and bitfield buffers themselves."""
+        cache = self.cache
+        cache.ensure(dev)
+        if not self.cache_loaded:
+            src = self.train_cfg.get("cache_load_from", None)
+            files = sorted(os.listdir(src)) if src is not None else []
+            if files:
+                assert len(files) == self.cache_size
+                sids = list(cache)
+                for start in range(0, len(sids), 8):                     # (a few files at a time: the shard need not fit in host memory)
+                    cache.import_entries({sid: torch.load(os.path.join(src, files[sid]), map_location="cpu") for sid in sids[start:start + 8]},
+                                         self.code_activation.inverse)
+            self.cache_loaded = True
+        sids = [int(sid) for sid in data["scene_id"]]
+        slots = cache.slots(sids)
+        held = [i for i, slot in enumerate(slots) if cache.present[slot]]     # batch entries whose slot is filled -> rows 0 .. of the buffers
+        row_of = {i: r for r, i in enumerate(held)}
+        grid = bits = None
+        if held:
+            leaf_rows, m, v, grid, bits = cache.batch_buffers(len(held))
+            cache.load([sids[i] for i in held], leaf_rows, m, v, grid, bits)
+        if len(held) < len(sids):                                            # fresh scenes in the batch: their rows sit between the loaded ones
+            grid_held, bits_held = grid, bits
+            grid, bits = self.get_init_density_grid(len(sids), dev), self.get_init_density_bitfield(len(sids), dev)
+            if held:
+                index = torch.tensor(held, device=dev)
+                grid.index_copy_(0, index, grid_held)
+                bits.index_copy_(0, index, bits_held)
+        leaves = [leaf_rows[row_of[i]].detach().requires_grad_(True) if i in row_of else self.get_init_code_(None, dev) for i in range(len(sids))]
+        optimizers = self.build_optimizer(leaves, self.train_cfg)
+        for i, (opt, slot) in enumerate(zip(optimizers, slots)):
+            if i in row_of and cache.has_state[slot]:
+                opt.state[leaves[i]] = dict(step=cache.step[slot].clone(), exp_avg=m[row_of[i]], exp_avg_sq=v[row_of[i]])
+        return leaves, optimizers, grid, bits
+
+    def _save_cache_device(self, code_list_, code_optimizers, density_grid, density_bitfield, scene_id, scene_name):
+        """``save_cache`` into the device cache: ONE launch for the batch; ``step``, names and ``param_groups`` are recorded on the host.  With
+        ``train_cfg['save_dir']`` the files are the slots' exports (one gather and one device-to-host copy for the batch)."""
+        from .scene_cache import _FileWriters
+        cache = self.cache
+        cache.ensure(get_module_device(self))
+        states, groups = [], []
+        for opt in code_optimizers:
+            sd = opt.state_dict()
+            if len(sd["state"]) > 1:
+                raise TypeError("cache_store='device': a code optimizer with more than one parameter")
+            states.append(dict(next(iter(sd["state"].values()))) if sd["state"] else {})
+            groups.append(sd["param_groups"])
+        keep = cache.store(list(scene_id), list(scene_name), list(code_list_), states, groups, density_grid, density_bitfield)
+        save_dir = self.train_cfg.get("save_dir", None)
+        if save_dir is None:
+            return
+        os.makedirs(save_dir, exist_ok=True)
+        if self.num_file_writers > 0 and self.file_writers is None:
+            self.file_writers = _FileWriters(save_dir, self.num_file_writers)
+        for i, record in zip(keep, cache.export([scene_id[i] for i in keep])):
+            if self.file_writers is not None:
+                self.file_writers.put(i, record)                          # (an export is a private copy already)
+            else:
+                torch.save(record, os.path.join(save_dir, scene_name[i] + ".pth"))
 
     def _conditioning(self, data, cfg) -> Conditioning:
         return Conditioning.from_batch(data, cfg.get("dt_gamma_scale", 0.0))
