@@ -3,7 +3,7 @@
 ROUND 6 -- what the pass is FOR now (the block at the end of this file: ``unpack_cross_half``, ``scan_packed_cross_half``): every packed fp32 instruction whose
 op_sel / op_sel_hi bits read across the halves of a VGPR source pair is split into two plain instructions, and the build fails if one is left in a linked code
 object.  That instruction kind is what made the fused render differ from run to run with two waves on a SIMD (rounds 2 - 5); the per-ray trace hashes and the
-in-kernel re-evaluation that found it are tools/trace_check.py and tools/blend_check.py.
+in-kernel re-evaluation that found it are described in profiles/r06/README.md.
 
 The rest of this docstring and the walk below are the two PADDING rules of rounds 3 and 5, kept for experiments and OFF in the default build (build.py): at least
 N issue slots (``wait_states``) between a transcendental VALU instruction and the instruction that reads its result, and (``SWAP_MFMA_WAIT_STATES``) between a
@@ -427,7 +427,7 @@ def verify_code_object(path: str, wait_states: int, objdump: str = "/opt/rocm/li
 # ---------------------------------------------------------------------------------------------- r06: packed fp32 instructions with cross-half operand selection
 #: Round 6 (profiles/r06/README.md).  The run-to-run differences of the shading kernel that need two waves per SIMD -- r02's "groups of 16
 #: neighbouring rays", r03's transcendental theory, r05's swap theory -- were traced, with per-ray hashes of every stage and an in-kernel re-evaluation
-#: (tools/trace_check.py, tools/blend_check.py), to ONE kind of instruction: a packed fp32 operation (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) whose `op_sel` / `op_sel_hi`
+#: (profiles/r06/README.md), to ONE kind of instruction: a packed fp32 operation (v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32) whose `op_sel` / `op_sel_hi`
 #: bits make a half of the result read the OTHER half of a VGPR source pair (the compiler's way of broadcasting one weight to both halves).  On gfx950 with two waves on a
 #: SIMD the low half of such an instruction's result occasionally comes out, in lanes 48-63 only, as if the product term were absent.  The same arithmetic as plain
 #: v_mul / v_fma, or packed with the broadcast materialised in a register pair, never does.  The library therefore contains NO such instruction: the sources avoid them

@@ -13,7 +13,8 @@ profiles/r06/README.md).  The build FAILS if one such instruction is left in a l
 transcendental, between a lane swap and a matrix instruction) are still in asm_postpass.py for experiments and are OFF by default (``SSDNERF_TRANS_USE_WAIT_STATES=1``
 is the toolchain's own distance, ``SSDNERF_SWAP_MFMA_WAIT_STATES=0``): with the crossed instructions gone, the compiler's own code is clean in every arrangement that
 used to fail and over 10^5 renders (profiles/r06/g_*, e_*).  ``SSDNERF_KEEP_PACKED_CROSS_HALF=1`` keeps the compiler's instructions (positive-control builds only);
-``SSDNERF_NO_POSTPASS=1`` builds with plain `hipcc -c`.  ``lib/postpass_report.json`` records what the pass did per source, the settings, and the toolchain.
+``SSDNERF_NO_POSTPASS=1`` builds with plain `hipcc -c`.  ``lib/postpass_report.json`` records what the pass did per source, the settings, the toolchain,
+a hash of each source's linked device code (``code_sha16``: what ``render_build_id`` binds a profiling session to) and one of the source text it was built from (``csrc_sha16``).
 
 The pass parses the device listing syntax of ROCm 7.2 and re-states `hipcc -c`'s internal device steps, so it is PINNED to the toolchains it was
 validated on (``VALIDATED_HIP_VERSIONS``): another `hipcc --version` fails the build loudly (``SSDNERF_ALLOW_UNVALIDATED_TOOLCHAIN=1`` overrides
@@ -22,6 +23,7 @@ repeated on it).
 """
 from __future__ import annotations
 
+import hashlib
 import json
 import os
 import subprocess
@@ -71,32 +73,55 @@ def toolchain() -> dict:
     return {"hip_version": hip, "clang": clang, "validated": bool(hip) and hip.startswith(VALIDATED_HIP_VERSIONS)}
 
 
-def render_build_id() -> dict:
-    """what decides the render kernels of the library that is loaded: a hash over the render path's sources, and the build settings and the post-pass's effect on those sources from the
-    shipped report.  tools/make_traffic_json.py stores it with a profiling session; bench.py quotes a session's HBM traffic only if it matches the library it times."""
-    import hashlib
+def _csrc_sha16() -> str:
+    """hash over the text of every source and header a report is built from: says whether a report belongs to this tree (report_is_current)"""
     h = hashlib.sha256()
-    for f in ["shade_mfma.hip", "render_queue.hip", "common.h", "decode_core.h", "sh_basis.h"]:
-        h.update(open(os.path.join(CSRC, f), "rb").read())
-    try:
-        with open(os.path.join(LIB_DIR, "postpass_report.json")) as f:
-            rep = json.load(f)
-        settings = rep.get("settings")
-        # what the post-pass DID to the two render sources (not the text of asm_postpass.py: a comment there changes no instruction)
-        effect = {k: {kk: rep["sources"][k].get(kk) for kk in ("packed_cross_half_split", "pairs_closer_than_required", "trans_instructions")}
-                  for k in ("shade_mfma.hip", "render_queue.hip") if k in rep.get("sources", {})}
-    except Exception:                                                # noqa: BLE001
-        settings, effect = None, None
-    return {"render_csrc_sha16": h.hexdigest()[:16], "build_settings": settings, "postpass_effect": effect}
+    for f in SOURCES + HEADERS:
+        with open(os.path.join(CSRC, f), "rb") as fh:
+            h.update(fh.read())
+    return h.hexdigest()[:16]
+
+
+def _code_sha16(dev_out: str) -> str:
+    """hash over what the device loads of a linked code object: its .note, .rodata, .text and .data bytes, in that order.  Not the whole file: its symbol
+    table carries a per-compilation __hip_cuid_<hash> name that changes with any edit of the source, a comment included."""
+    h = hashlib.sha256()
+    for sec in (".note", ".rodata", ".text", ".data"):
+        raw = dev_out + sec + ".bin"
+        subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "-O", "binary", f"--only-section={sec}", dev_out, raw], check=True, capture_output=True)
+        with open(raw, "rb") as f:                                   # (a section the code object does not have comes out empty)
+            h.update(f.read())
+        os.remove(raw)
+    return h.hexdigest()[:16]
+
+
+def _report() -> dict:
+    with open(os.path.join(LIB_DIR, "postpass_report.json")) as f:
+        return json.load(f)
+
+
+def report_is_current() -> bool:
+    """the report in LIB_DIR was built from the sources and headers of this tree"""
+    return _report().get("csrc_sha16") == _csrc_sha16()
+
+
+def render_build_id() -> dict:
+    """what decides the render kernels of the library that is loaded, all of it from the report in LIB_DIR: the hashes of the two render sources' device code, the build settings, and the
+    post-pass's effect on those sources.  tools/make_traffic_json.py stores it with a profiling session; bench.py quotes a session's HBM traffic only if it matches the library it times.
+    A missing report raises."""
+    rep = _report()
+    render = ("shade_mfma.hip", "render_queue.hip")
+    # what the post-pass DID to the two render sources (not the text of asm_postpass.py: a comment there changes no instruction)
+    effect = {k: {kk: rep["sources"][k].get(kk) for kk in ("packed_cross_half_split", "pairs_closer_than_required", "trans_instructions")} for k in render}
+    return {"render_code_sha16": {k: rep["sources"][k]["code_sha16"] for k in render}, "build_settings": rep.get("settings"), "postpass_effect": effect}
 
 
 def needs_build() -> bool:
     if not os.path.exists(LIB_PATH):
         return True
     try:
-        with open(os.path.join(LIB_DIR, "postpass_report.json")) as f:
-            if json.load(f).get("settings") != _settings():
-                return True                                          # SSDNERF_TRANS_USE_WAIT_STATES / SSDNERF_NO_POSTPASS / SSDNERF_EXTRA_FLAGS changed
+        if _report().get("settings") != _settings():
+            return True                                              # SSDNERF_TRANS_USE_WAIT_STATES / SSDNERF_NO_POSTPASS / SSDNERF_EXTRA_FLAGS changed
     except Exception:                                                # noqa: BLE001
         return True
     t = os.path.getmtime(LIB_PATH)
@@ -158,6 +183,7 @@ def _compile_with_postpass(src: str, obj: str, verbose: bool) -> dict:
         if left:
             raise RuntimeError(f"{src}: packed fp32 instructions with a crossed VGPR source are left in the linked code object: {left}")
         stats["code_object_check"]["packed_cross_half"] = 0
+    stats["code_sha16"] = _code_sha16(dev_out)
     _run([os.path.join(LLVM_BIN, "clang-offload-bundler"), "-type=o", "-bundle-align=4096",
           "-targets=host-x86_64-unknown-linux-gnu,hipv4-amdgcn-amd-amdhsa--gfx950", "-input=/dev/null", f"-input={dev_out}", f"-output={fatbin}"], verbose)
     _run([_hipcc()] + flags + ["--cuda-host-only", "-Xclang", "-fcuda-include-gpubinary", "-Xclang", fatbin, "-c", src, "-o", obj], verbose)
@@ -177,7 +203,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
                            f"{tc.get('hip_version')!r} ({tc.get('clang')}).  The pass parses the device listing and re-states hipcc's device link line; "
                            "re-run the hazard checks on this toolchain (build.py docstring), then set SSDNERF_ALLOW_UNVALIDATED_TOOLCHAIN=1 or extend "
                            "VALIDATED_HIP_VERSIONS.")
-    objs, report = [], {"wait_states": TRANS_USE_WAIT_STATES if postpass else None, "settings": _settings(), "toolchain": tc, "sources": {}}
+    objs, report = [], {"wait_states": TRANS_USE_WAIT_STATES if postpass else None, "settings": _settings(), "toolchain": tc, "csrc_sha16": _csrc_sha16(), "sources": {}}
     for src in SOURCES:
         obj = os.path.join(LIB_DIR, src.replace(".hip", ".o"))
         if postpass:

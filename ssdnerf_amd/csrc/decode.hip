@@ -221,12 +221,7 @@ __global__ void __launch_bounds__(DEC_TPB) k_decode_bwd_feat(const PT* __restric
     float f[18], gf[18], sh[16];
     ssd_gather18<PT>(planes + scene * plane_stride, g, x, y, z, f);
     if (COLOR) shb::eval<4, false>(dirs[3ull * i], dirs[3ull * i + 1], dirs[3ull * i + 2], sh, nullptr, nullptr, nullptr);
-#ifdef DB_EXP_NO_MLP                                                             // (measurement only: everything of the kernel but the MLP)
-#pragma unroll
-    for (int k = 0; k < 18; ++k) gf[k] = f[k] * gs + (COLOR ? sh[k & 15] * gc[k % 3] : 0.0f);
-#else
     ssdb_mlp_backward(P, f, COLOR ? sh : f, sat, gs, gc, COLOR ? 1 : 0, gf);
-#endif
     const float us[3] = {x, x, y}, vs[3] = {y, z, z};
 #pragma unroll
     for (int p = 0; p < 3; ++p) {
@@ -589,13 +584,8 @@ __global__ void __launch_bounds__(DEC_TPB) k_decode_bwd_bin(const uint32_t* __re
                 // (a clamped border corner, x1 == x0, carries weight 0 in every sample of the run: its sum is +-0 and adding it changes nothing)
                 if (lx < DB_TILE && ly < DB_TILE) {
                     float* t = acc + (ly * DB_TILE + lx) * 6;
-#ifdef DB_EXP_NO_ATOMICS                                                         // (measurement only: racy plain adds -- what the pass costs without the LDS atomics)
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) t[c] += v[q][c];
-#else
 #pragma unroll
                     for (int c = 0; c < 6; ++c) atomicAdd(t + c, v[q][c]);
-#endif
                 }
             }
         }
@@ -630,9 +620,7 @@ __global__ void __launch_bounds__(DEC_TPB) k_decode_bwd_bin(const uint32_t* __re
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll 1
         while (cnt >= 64) {
-#ifndef DB_EXP_SCAN_ONLY                                                          // (measurement only: the key scan and the lists alone)
             add_listed(64);
-#endif
             head = (head + 64) % DB_LIST;
             cnt -= 64;
         }
@@ -652,7 +640,7 @@ __global__ void __launch_bounds__(DEC_TPB) k_decode_bwd_bin(const uint32_t* __re
     }
 }
 
-// r06: the same reduction WITHOUT floating-point LDS atomics.  tools/r06_decode_bwd_split.sh: of k_decode_bwd_bin's 2.7 ms (7 M uniform samples; 1.9 ms ray-ordered)
+// r06: the same reduction WITHOUT floating-point LDS atomics.  profiles/r06/y_decode_bwd_split.txt (side builds without the atomics / with the key scan alone): of k_decode_bwd_bin's 2.7 ms (7 M uniform samples; 1.9 ms ray-ordered)
 // 0.64 ms are the key scan, the lists, the contributions and the tile stores -- the rest is `ds_add_f32`, which the LDS retires at ~2.4 cycles PER LANE (a 64-lane
 // instruction ~150 cycles; plain 4-byte reads and writes run at 32 lanes per cycle).  So the additions become plain read-modify-writes, made safe by OWNERSHIP:
 //   * the tile's four 16 x 16 quadrants belong to the block's four waves -- no two waves ever touch the same texel.  The waves still share the key scan (each scans a quarter
@@ -811,9 +799,7 @@ __global__ void __launch_bounds__(DEC_TPB) k_decode_bwd_bin_owned(const uint32_t
         const uint32_t tail_now = *reinterpret_cast<volatile uint32_t*>(&qtail[wave]);
 #pragma unroll 1
         while (tail_now - head >= 64u) {
-#ifndef DB_EXP_SCAN_ONLY
             add_listed(64);
-#endif
             head += 64u;
         }
         __syncthreads();                                                                      // every ring is below 64 before the next step's (at most 1024) items arrive

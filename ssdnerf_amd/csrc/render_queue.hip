@@ -57,10 +57,6 @@ SSD_DEV int rq_cell(const FastMarch& m, float v) { return (int)fminf(v * m.half_
 struct FastProbe { float x, y, z, dt; int nx, ny, nz; bool occ; };
 
 // DTG0: dt_gamma == 0 (the uncond render), where clamp(t * 0, dt_min, dt_max) == dt_min: the march step is a constant
-#ifndef RQ_RUN_TO_CLOSED
-#define RQ_RUN_TO_CLOSED 0                     // (r05) 1: `do t += dt while (t < tt)` with the constant step as ssd_run_to_const (common.h): bit-identical, and no
-                                               // faster here (stage A 0.80 ms either way: profiles/r05) -- off
-#endif
 template <bool DTG0>
 SSD_DEV float rq_dt(const FastMarch& m, float t) { return DTG0 ? m.dt_min : ssd_clamp(t * m.dt_gamma, m.dt_min, m.dt_max); }
 
@@ -86,7 +82,8 @@ SSD_DEV float rq_skip(const FastMarch& m, const RayGeom& r, const FastProbe& p, 
     const float ty = ssd_fma(ssd_fma((float)p.ny + sgy, m.two_rH, -1.0f), m.mip_bound, -p.y) * r.rdy;
     const float tz = ssd_fma(ssd_fma((float)p.nz + sgz, m.two_rH, -1.0f), m.mip_bound, -p.z) * r.rdz;
     const float tt = t + fmaxf(0.0f, fminf(tx, fminf(ty, tz)));
-    if (DTG0 && RQ_RUN_TO_CLOSED) return ssd_run_to_const(m.dt_min, t, tt);      // (r05) the same chain of additions in closed form: common.h
+    // (r05, measured and dropped: with the constant step, common.h's closed form ssd_run_to_const for this loop and the block exits below -- bit-identical, and no
+    // faster here: stage A 0.80 ms either way, profiles/r05)
     do {
         t += rq_dt<DTG0>(m, t);
     } while (t < tt);
@@ -535,8 +532,7 @@ __global__ void __launch_bounds__(RQ_MTPB) k_survivor_march(QueueCfg c, RaySrc s
                             continue;
                         }
                     }
-                    if (DTG0 && RQ_RUN_TO_CLOSED) t = ssd_run_to_const(c.m.dt_min, t, tt);
-                    else do { t += rq_dt<DTG0>(c.m, t); } while (t < tt);
+                    do { t += rq_dt<DTG0>(c.m, t); } while (t < tt);
                 }
             } else {
                 while (t < far_) {

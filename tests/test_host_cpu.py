@@ -345,22 +345,34 @@ def test_pre_split_convolution_planning_is_host_logic():
     assert lib.ssdnerf_split_f32_nhwc(None, None, ctypes.c_uint64(0), u32(32), ctypes.c_uint64(0), None) == 0                # empty: a no-op
 
 
-def test_traffic_figure_is_bound_to_the_render_build():
-    """bench.py quotes profiles/traffic_latest.json's HBM bytes only for a library built from the render sources and settings the profiling session ran on
-    (``build.render_build_id``): the committed session must match the tree, and a changed source must be noticed"""
+def test_traffic_figure_is_bound_to_the_render_build(tmp_path, monkeypatch):
+    """bench.py quotes profiles/traffic_latest.json's HBM bytes only for a library whose render kernels are, byte for byte, the device code the profiling session ran
+    (``build.render_build_id``, read from the build's report): the committed session must match the tree, and another code object must be noticed"""
     import json
     import os
+    import pytest
     from ssdnerf_amd import build as B
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     tj = json.load(open(os.path.join(root, "profiles", "traffic_latest.json")))
     mine = B.render_build_id()
-    assert set(mine) == {"render_csrc_sha16", "build_settings", "postpass_effect"} and len(mine["render_csrc_sha16"]) == 16
-    assert tj["render_build_id"] == mine, "the render sources or build settings changed since tools/prof_render.sh last ran: rerun it (tools/r06_final.sh) and commit profiles/"
-    saved = B.CSRC
-    try:
-        B.CSRC = os.path.join(root, "tests", "host")                      # (other files under the same names would hash differently; a missing one raises)
-        import pytest
-        with pytest.raises(FileNotFoundError):
-            B.render_build_id()
-    finally:
-        B.CSRC = saved
+    assert set(mine) == {"render_code_sha16", "build_settings", "postpass_effect"}
+    assert set(mine["render_code_sha16"]) == {"shade_mfma.hip", "render_queue.hip"} and all(len(v) == 16 for v in mine["render_code_sha16"].values())
+    # the report the id is read from belongs to THIS tree: a kernel edit without a rebuilt and committed report fails here
+    assert B.report_is_current(), "csrc/ or include/ changed since ssdnerf_amd/lib/postpass_report.json was written: rebuild (python -m ssdnerf_amd.build --force) and commit the report"
+    assert tj["render_build_id"] == mine, ("the render kernels' device code or the build settings changed since tools/prof_render.sh last ran: "
+                                           "rerun tools/prof_render.sh on this build and commit profiles/")
+    with open(os.path.join(B.LIB_DIR, "postpass_report.json")) as f:
+        rep = json.load(f)
+    monkeypatch.setattr(B, "LIB_DIR", str(tmp_path))
+    with pytest.raises(FileNotFoundError):                                # no report, no id
+        B.render_build_id()
+    for src in ("shade_mfma.hip", "render_queue.hip"):                    # another code object under either name gives another id
+        other = json.loads(json.dumps(rep))
+        other["sources"][src]["code_sha16"] = "0" * 16
+        (tmp_path / "postpass_report.json").write_text(json.dumps(other))
+        assert B.render_build_id() != mine and B.render_build_id()["render_code_sha16"][src] == "0" * 16
+    (tmp_path / "postpass_report.json").write_text(json.dumps(rep))
+    assert B.render_build_id() == mine and B.report_is_current()
+    rep["csrc_sha16"] = "0" * 16                                          # a report of other sources is not current
+    (tmp_path / "postpass_report.json").write_text(json.dumps(rep))
+    assert not B.report_is_current()

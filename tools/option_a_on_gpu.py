@@ -4,8 +4,8 @@
 (lib/models/decoders/base_volume_renderer.py:41-133) run unmodified, with `import _raymarching` / `import _shencoder` resolving to
 ssdnerf_amd/dropin (ctypes over libssdnerf_hip.so).  Renders the fixtures' 64x64 view (eval branch, both dt_gamma values, and the train
 branch with its backward) and compares with tests/golden/render_*_64*.npz, which the same reference code produced on the CPU with its own
-kernels.  Needs a copy of the reference's Python: /root/reference in the build container, or REF=<dir> (tools/stage_reference.sh stages
-lib/ into the git-ignored oracle/_ref/reference_py so that it travels to the GPU box; nothing of it is committed).  Skips without one."""
+kernels.  Needs a copy of the reference's Python: /root/reference in the build container, or REF=<dir> (nothing of it is committed, and it
+does not travel to the GPU box).  Skips without one."""
 import importlib
 import os
 import sys
@@ -20,7 +20,7 @@ sys.path.insert(0, GOLD)
 
 
 def main():
-    ref = os.environ.get("REF") or ("/root/reference" if os.path.isdir("/root/reference") else os.path.join(ROOT, "oracle", "_ref", "reference_py"))
+    ref = os.environ.get("REF") or "/root/reference"
     if not os.path.isdir(os.path.join(ref, "lib", "ops")):
         print(f"option A: no reference checkout at {ref}: skipped")
         return 0

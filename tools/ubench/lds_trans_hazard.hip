@@ -1,7 +1,7 @@
 // tools/ubench/lds_trans_hazard.hip -- stand-alone probe for the run-to-run differences of k_shade_mfma (profiles/r05/m_* and r_*).
 //
 // r05 evidence from the full kernel: arrangements of the SiLU "heads" that differ only in WHERE the group's LDS weight reads sit relative to its burst of
-// v_exp_f32 (in front of it: -DSM_W_EARLY=1) or in how many pairs a group holds (-DSM_QB={0,2,4,7,10,13,16}) give renders that differ from run to run on
+// v_exp_f32 (in front of it, the form that ships since r06, or behind it) or in how many pairs a group holds (-DSM_QB={0,2,4,7,10,13,16}) give renders that differ from run to run on
 // groups of rays, at EVERY transcendental -> use distance the post-pass enforces for the failing grouping up to 6 (and none at 7+), while the shipped
 // arrangement is clean at every distance including the compiler's own.  So the distance rule is not the whole story; the suspects are the units that
 // write VGPRs asynchronously beside the VALU: LDS return data, the quarter-rate transcendental unit, the matrix unit.
@@ -47,10 +47,10 @@ __global__ void __launch_bounds__(256, 2) k_probe(unsigned* bad, const float* in
         const unsigned addr = (((lane >> 5) * 3 + (unsigned)(it & 15) * 6) * 16) & 0xffff;     // broadcast within a lane half, like the output weights
         float f0, f1, s0, s1;
         if (MF) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(za, za, acc, 0, 0, 0);
-        if (ORDER == 0)       // LDS reads behind the exp burst (the shipped arrangement)
+        if (ORDER == 0)       // LDS reads behind the exp burst (the arrangement shipped in r05)
             asm volatile(SETUP EXPS LDSR ADDS RCPS NOPS(0) MULS "s_waitcnt lgkmcnt(0)\n" FMAS "s_nop 7\nv_mov_b32 %0, v124\nv_mov_b32 %1, v125\n"
                          : "=v"(f0), "=v"(f1) : "v"(addr), "v"(x) : CLOB);
-        else                  // LDS reads in front of it (-DSM_W_EARLY=1)
+        else                  // LDS reads in front of it (shipped since r06)
             asm volatile(SETUP LDSR EXPS ADDS RCPS NOPS(0) MULS "s_waitcnt lgkmcnt(0)\n" FMAS "s_nop 7\nv_mov_b32 %0, v124\nv_mov_b32 %1, v125\n"
                          : "=v"(f0), "=v"(f1) : "v"(addr), "v"(x) : CLOB);
         // the same arithmetic, every producer far from its consumer
