@@ -280,6 +280,17 @@ int ssdnerf_packbits_dev_thresh(const void* grid, int grid_dtype, uint32_t N, co
 int ssdnerf_ddim_step_v(const float* x_t, const float* v, uint64_t n, float sqrt_ab, float sqrt_1mab, float sqrt_ab_prev,
                         float dir_coef, float clip_lo, float clip_hi, float* x0_out, float* xprev_out, void* stream);
 
+/* One DPM-Solver++(2M) step of the latent in V-parameterisation (Lu et al. 2022, data prediction, multistep; no counterpart in the reference):
+ *   x0 = clamp(sqrt_ab * x_t - sqrt_1mab * v, lo, hi);   x_next = c * x0 + d * x_t + e * x0_prev,
+ * with lambda = log(sqrt_ab / sqrt_1mab), h = lambda_prev - lambda_t, phi = -expm1(-h), r = h_of_the_step_before / h:
+ *   d = sqrt_1mab_prev / sqrt_1mab,  c = sqrt_ab_prev phi (1 + 1/(2r)),  e = -sqrt_ab_prev phi / (2r);   first-order step: c = sqrt_ab_prev phi, e = 0.
+ * n elements (multiple of 4; 0 is a no-op).  x0_prev may be NULL only when e == 0 (it is not read then).  xnext_out may alias x_t and x0_out may
+ * alias v (element i is read before it is written); x0_out == x0_prev fails with SSDNERF_E_INVALID, as every refusal does, before any launch.
+ * ssdnerf_dpmpp_block_cap(): the cap on the number of 256-lane blocks; larger inputs go round the grid-stride loop. */
+int ssdnerf_dpmpp_step_v(const float* x_t, const float* v, const float* x0_prev, uint64_t n, float sqrt_ab, float sqrt_1mab, float c,
+                         float d, float e, float clip_lo, float clip_hi, float* x0_out, float* xnext_out, void* stream);
+uint32_t ssdnerf_dpmpp_block_cap(void);
+
 /* Camera rays of n_views pinhole views (get_cam_rays, lib/core/utils/nerf_utils.py:17-61): c2w [n_views][4][4] row-major,
  * intrinsics [n_views][4] = {fx, fy, cx, cy}; rays_o, rays_d [n_views][h][w][3]: pixel-centre (x + 0.5) directions rotated by
  * c2w[:3,:3] and L2-normalised, origins c2w[:3,3] broadcast. */

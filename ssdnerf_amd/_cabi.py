@@ -38,6 +38,7 @@ EXPORTS = [
     "ssdnerf_gather_views_u8", "ssdnerf_sample_rays_u8",
     "ssdnerf_ema_chunk", "ssdnerf_ema_plan_build", "ssdnerf_ema_update_multi",
     "ssdnerf_cache_max_scenes", "ssdnerf_cache_load_multi", "ssdnerf_cache_store_multi",
+    "ssdnerf_dpmpp_step_v", "ssdnerf_dpmpp_block_cap",
 ]
 
 
@@ -124,6 +125,9 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_cache_max_scenes.argtypes = []
         for fn in (l.ssdnerf_cache_load_multi, l.ssdnerf_cache_store_multi):
             fn.argtypes = [ctypes.POINTER(CacheStore), ctypes.POINTER(CacheRow), ctypes.c_uint32] + [ctypes.c_void_p] * 6
+        l.ssdnerf_dpmpp_block_cap.restype = ctypes.c_uint32
+        l.ssdnerf_dpmpp_block_cap.argtypes = []
+        l.ssdnerf_dpmpp_step_v.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_float] * 7 + [ctypes.c_void_p] * 3
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -10,6 +10,8 @@ methods are the reference's; the implementation is organised for the MI355X inst
 * An unguided DDIM step is: write ``t`` into the UNet session's static buffer, replay the captured forward (``unet_fast.UnetSession``), ONE
   fused elementwise launch (``ssdnerf_ddim_step_v``) that turns (x_t, v) into (x0, x_prev) and writes x_prev back IN PLACE into the
   session's input buffer.  Three launches per step, no copies, no allocation, no host sync in the loop.
+* ``sample_method='dpmpp_2m'`` (not in the reference, opt-in): DPM-Solver++(2M) over the same timesteps -- the same evaluation per step, and a fused update
+  (``ssdnerf_dpmpp_step_v``) that also reads the x0 of the step before from one of two alternating history buffers.
 * The guided step (rendering guidance, SSDNeRF's ``grad_guide_fn``) needs autograd through the UNet and the renderer; it keeps tensors in
   the graph exactly where the reference does, with the coefficients coming from the plan as Python floats.
 """
@@ -128,7 +130,8 @@ class PlanStep:
     eps = (x_t - a x0) / b, the latent becomes
         kind 'ddim'     :  c x0 + d eps + n z            (c = sqrt(abar_prev), d = sqrt(1 - abar_prev - eta^2 var), n = eta sqrt(var))
         kind 'langevin' :  x_t - d eps + n z             (d = delta b / 2, n = sqrt(delta) b)
-        kind 'ddpm'     :  c x0 + d x_t + n z            (posterior mean coefficients, n = sqrt(var), 0 at t = 0)"""
+        kind 'ddpm'     :  c x0 + d x_t + n z            (posterior mean coefficients, n = sqrt(var), 0 at t = 0)
+        kind 'dpmpp'    :  c x0 + d x_t + e x0_prev      (DPM-Solver++(2M); x0_prev: the clipped x0 of the step before; see SamplingPlan)"""
     kind: str
     t: int
     a: float
@@ -137,14 +140,16 @@ class PlanStep:
     d: float
     n: float
     emit: bool            # a trajectory point of the reference's ``save_intermediates`` list (the DDIM steps, not the Langevin corrections)
+    e: float = 0.0        # weight of the previous step's x0 (kind 'dpmpp', second-order steps only)
 
 
 class SamplingPlan:
-    """The whole trajectory of ``ddim_sample`` / ``ddpm_sample`` as a list of ``PlanStep``s (timesteps arange(T-1, -1, -T/n).long(): 50 ->
-    999, 979, ..., 19; 75 -> 999, 985, 972, ..., 12; the last DDIM step lands on alpha_bar_prev[0] = 1, i.e. x_prev = x0 exactly)."""
+    """The whole trajectory of ``ddim_sample`` / ``ddpm_sample`` / ``dpmpp_2m_sample`` as a list of ``PlanStep``s (timesteps arange(T-1, -1,
+    -T/n).long(): 50 -> 999, 979, ..., 19; 75 -> 999, 985, 972, ..., 12; the last DDIM step lands on alpha_bar_prev[0] = 1, i.e. x_prev = x0
+    exactly, and so does the last step of 'dpmpp_2m').  ``solver_order`` (1 or 2) belongs to 'dpmpp_2m' alone."""
 
     def __init__(self, sched: NoiseSchedule, method: str, n: int, eta: float = 0.0, langevin_steps: int = 0, langevin_delta: float = 0.1,
-                 langevin_t_range: Sequence[float] = (0, 1000), var_mode: str = "FIXED_LARGE"):
+                 langevin_t_range: Sequence[float] = (0, 1000), var_mode: str = "FIXED_LARGE", solver_order: int = 2):
         T = sched.T
         self.timesteps = torch.arange(start=T - 1, end=-1, step=-(T / n)).long()
         ts = self.timesteps.tolist()
@@ -171,6 +176,31 @@ class SamplingPlan:
             for t in ts:
                 steps.append(PlanStep("ddpm", t, float(sa[t]), float(sb[t]), float(sched["tilde_mu_t_coef1"][t]), float(sched["tilde_mu_t_coef2"][t]),
                                       float(np.sqrt(table[t])) if t != 0 else 0.0, True))
+        elif method == "dpmpp_2m":
+            # DPM-Solver++(2M) (Lu et al. 2022, data prediction): with lambda = log a - log b, h = lambda_prev - lambda_t, phi = -expm1(-h),
+            #   x_prev = (b_prev / b_t) x_t + a_prev phi D,    D = x0 (first order)  or  (1 + 1/(2r)) x0 - (1/(2r)) x0_prev,  r = h_before / h.
+            # The first-order step IS the eta = 0 DDIM step: a_prev phi = a_prev - b_prev a_t / b_t.  Same timesteps, one network evaluation each.
+            if solver_order not in (1, 2):
+                raise ValueError(f"dpmpp_2m: solver_order must be 1 or 2, not {solver_order!r}")
+            if langevin_steps > 0:
+                raise ValueError("dpmpp_2m: Langevin corrections move x_t between the two history points of a multistep update (langevin_steps must be 0)")
+            if eta != 0:
+                raise ValueError("dpmpp_2m is the deterministic solver (eta must be 0)")
+            lam = np.log(sa) - np.log(sb)
+            h_before = None
+            for i, t in enumerate(ts):
+                if i + 1 == len(ts):                                         # t_prev = -1: abar_prev = 1, lambda_prev = inf, phi = 1: x_prev = x0 exactly
+                    steps.append(PlanStep("dpmpp", t, float(sa[t]), float(sb[t]), 1.0, 0.0, 0.0, True, 0.0))
+                    break
+                t_prev = ts[i + 1]
+                h = lam[t_prev] - lam[t]
+                base = sa[t_prev] * -np.expm1(-h)
+                c, e = base, 0.0
+                if solver_order == 2 and h_before is not None:
+                    r = h_before / h
+                    c, e = base * (1 + 1 / (2 * r)), -base / (2 * r)
+                steps.append(PlanStep("dpmpp", t, float(sa[t]), float(sb[t]), float(c), float(sb[t_prev] / sb[t]), 0.0, True, float(e)))
+                h_before = h
         else:
             raise AttributeError(f"Cannot find sample method [{method}_sample] correspond to [{method}].")
         self.steps = steps
@@ -343,7 +373,7 @@ class GaussianDiffusion(nn.Module):
     def sampling_plan(self, method="ddim", cfg=None) -> SamplingPlan:
         cfg = self.test_cfg if cfg is None else cfg
         key = (method, cfg.get("num_timesteps", self.num_timesteps), cfg.get("eta", 0), cfg.get("langevin_steps", 0), cfg.get("langevin_delta", 0.1),
-               tuple(cfg.get("langevin_t_range", [0, 1000])), self.denoising_var_mode)
+               tuple(cfg.get("langevin_t_range", [0, 1000])), self.denoising_var_mode, cfg.get("solver_order", 2))
         if key not in self._plans:
             self._plans[key] = SamplingPlan(self.schedule, *key)
         return self._plans[key]
@@ -402,8 +432,11 @@ class GaussianDiffusion(nn.Module):
         return x0, out
 
     # ------------------------------------------------------------------------------------------ sampling
-    def _advance(self, s: PlanStep, x_t, x0, noise=None):
+    def _advance(self, s: PlanStep, x_t, x0, noise=None, x0_prev=None):
         """the latent after plan step ``s`` (see PlanStep)"""
+        if s.kind == "dpmpp":
+            x = s.c * x0 + s.d * x_t
+            return x + s.e * x0_prev if s.e != 0 else x
         if s.kind == "ddpm":
             x = s.c * x0 + s.d * x_t
         else:
@@ -429,6 +462,7 @@ class GaussianDiffusion(nn.Module):
             session = self.denoising.inference_session(x_t, t_rows[0])
             if session is not None:
                 session.x.copy_(x_t)                                         # the latent lives in the UNet's static input buffer from here on
+        history, x0_prev = None, None                                        # 'dpmpp': the two alternating x0 buffers of the fused step / the generic branch's last x0
         pending_x0 = None                                                    # x0 of the last emitting (DDIM) step; its trajectory point is the latent AFTER
                                                                              # the Langevin corrections that follow it (gaussian_diffusion.py:313-326)
         for i, s in enumerate(plan):
@@ -446,13 +480,28 @@ class GaussianDiffusion(nn.Module):
                 if kept is not None:
                     pending_x0 = x0
                 continue
+            if session is not None and s.kind == "dpmpp":
+                # ---- device-resident DPM-Solver++(2M) step: as above, and the update also reads the x0 the step before left in the other history buffer
+                if history is None:
+                    history = [torch.empty_like(session.x), torch.empty_like(session.x)]     # allocated once per call; they alternate
+                session.t.copy_(t_rows[i])
+                v = session.run()
+                x0 = history[i & 1]
+                C.check(C.lib().ssdnerf_dpmpp_step_v(C.ptr(session.x), C.ptr(v), C.ptr(history[(i & 1) ^ 1] if s.e != 0 else None),
+                                                     C.ctypes.c_uint64(v.numel()), C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d), C.f32(s.e),
+                                                     C.f32(clip[0]), C.f32(clip[1]), C.ptr(x0), C.ptr(session.x), C.stream()), "dpmpp_step_v")
+                if kept is not None:
+                    pending_x0 = x0.clone()                                  # (the buffer is written again two steps on)
+                continue
             if session is not None:                                          # a step kind the fused form does not cover: leave the session
                 x_t, session = session.x.clone(), None
             # a step that injects noise (Langevin, ancestral DDPM, eta > 0): the HOST draw first -- the device still has the previous step's work queued, the
             # draw (4.8 ms for 8 cars latents) hides under it; same generator, same order of draws as drawing inside _advance
             step_noise = _host_noise(x_t) if (s.n != 0 or s.kind == "ddpm") else None
             x0, _ = self.pred_x_0(x_t, t_rows[i], grad_guide_fn=grad_guide_fn, concat_cond=cond, cfg=cfg, **kwargs)
-            x_t = self._advance(s, x_t.detach() if grad_guide_fn is not None else x_t, x0, noise=step_noise)
+            x_t = self._advance(s, x_t.detach() if grad_guide_fn is not None else x_t, x0, noise=step_noise, x0_prev=x0_prev)
+            if s.kind == "dpmpp":
+                x0_prev = x0                                                 # (with guidance: the guided, clipped x0 that pred_x_0 returned)
             if kept is not None and s.emit:
                 pending_x0 = x0
         if session is not None:
@@ -466,6 +515,12 @@ class GaussianDiffusion(nn.Module):
 
     def ddpm_sample(self, noise, show_pbar=False, concat_cond=None, **kwargs):
         return self._run_plan(self.sampling_plan("ddpm"), noise, concat_cond, False, **kwargs)
+
+    def dpmpp_2m_sample(self, noise, show_pbar=False, concat_cond=None, save_intermediates=False, **kwargs):
+        """DPM-Solver++(2M) over the DDIM timesteps (not in the reference; opt in with ``test_cfg['sample_method'] = 'dpmpp_2m'`` or the constructor's
+        ``sample_method``): the same network evaluation, x0 prediction, clipping and guidance hook per step as ``ddim_sample``, a second-order update
+        from the last two x0.  ``test_cfg['solver_order']`` 1 gives DDIM's own trajectory."""
+        return self._run_plan(self.sampling_plan("dpmpp_2m"), noise, concat_cond, save_intermediates, **kwargs)
 
     # single-step entry points of the reference API (each resolves its coefficients like one plan entry)
     def p_sample_ddim(self, x_t, t, t_prev, noise=None, cfg=dict(), grad_guide_fn=None, **kwargs):
@@ -499,9 +554,10 @@ class GaussianDiffusion(nn.Module):
         return self._advance(s, x_t, x0, noise), x0
 
     def sample_from_noise(self, noise, **kwargs):
-        method = self.sample_method.lower()
-        if method not in ("ddim", "ddpm"):
-            raise AttributeError(f"Cannot find sample method [{method}_sample] correspond to [{self.sample_method}].")
+        name = self.test_cfg.get("sample_method", self.sample_method)       # (no config of the reference sets the test_cfg key)
+        method = name.lower()
+        if method not in ("ddim", "ddpm", "dpmpp_2m"):
+            raise AttributeError(f"Cannot find sample method [{method}_sample] correspond to [{name}].")
         return getattr(self, f"{method}_sample")(noise=noise, **kwargs)
 
     # ------------------------------------------------------------------------------------------ prior loss
