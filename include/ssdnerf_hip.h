@@ -661,6 +661,21 @@ size_t ssdnerf_kid_subset_sums_workspace(uint32_t num_subsets, uint32_t m);
 int ssdnerf_kid_subset_sums(const float* fake, const float* real, const int64_t* idx_fake, const int64_t* idx_real, uint32_t num_subsets, uint32_t m,
                             uint32_t D, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- PNG output: what is per pixel and per row, in front of the host's deflate (csrc/png_rows.hip) ------------------------------
+ * n images -> n streams of h filtered scanlines, out uint8 [n][h][1 + 3 W]: W = w without a target, 2 w with one (target left, pred right; the left
+ * neighbour of pred's first pixel is target's last).  pred, target: [n][h][w][3], fp32 (*_is_u8 == 0) or uint8 (taken as they are); target nullable.
+ * Bytes of an fp32 pred: rint(clamp(x, 0, 1) * 255), ties to even (ssdnerf_quantize_u8); of an fp32 target: (uint8)(clamp(t, 0, 1) * 255), truncated;
+ * NaN -> 0 in both.  Per row all five filter types of the PNG specification (8-bit RGB, bpp = 3; Average floors, Paeth breaks ties a, b, c) are scored
+ * by sum(min(r, 256 - r)) over the filtered bytes r; the lowest score wins, a tie goes to the lowest type; the row is [type, filtered bytes].
+ * No atomics: two calls return the same bytes.  n == 0 is a no-op; h == 0, w == 0 or w > 2^28 fail with SSDNERF_E_INVALID. */
+int ssdnerf_png_filter_rows(const void* pred, int pred_is_u8, const void* target, int target_is_u8, uint32_t n, uint32_t h, uint32_t w, uint8_t* out,
+                            void* stream);
+/* code fp32 [S][3][C][h][w] -> out uint8 [S][3 h][C w][3]: the reference's plane sheet (rows reversed within a plane unless flip_z; plane p, row y,
+ * channel c, column x at out[s][p h + y][c w + x]) through table uint8 [256][3] as matplotlib maps a float32 array: t = (x - vmin) / (vmax - vmin) in
+ * fp32, NaN -> (0, 0, 0), t < 0 -> entry 0, t >= 1 -> entry 255, else entry floor(t * 256). */
+int ssdnerf_code_plane_rgb(const float* code, const uint8_t* table, uint32_t S, uint32_t C, uint32_t h, uint32_t w, float vmin, float vmax, int flip_z,
+                           uint8_t* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

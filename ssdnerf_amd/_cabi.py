@@ -39,6 +39,7 @@ EXPORTS = [
     "ssdnerf_ema_chunk", "ssdnerf_ema_plan_build", "ssdnerf_ema_update_multi",
     "ssdnerf_cache_max_scenes", "ssdnerf_cache_load_multi", "ssdnerf_cache_store_multi",
     "ssdnerf_dpmpp_step_v", "ssdnerf_dpmpp_block_cap",
+    "ssdnerf_png_filter_rows", "ssdnerf_code_plane_rgb",
 ]
 
 
@@ -128,6 +129,8 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_dpmpp_block_cap.restype = ctypes.c_uint32
         l.ssdnerf_dpmpp_block_cap.argtypes = []
         l.ssdnerf_dpmpp_step_v.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_float] * 7 + [ctypes.c_void_p] * 3
+        l.ssdnerf_png_filter_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 2
+        l.ssdnerf_code_plane_rgb.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")
         _lib = l

@@ -506,6 +506,13 @@ class TriPlaneDecoder(VolumeRenderer):
         sigmas, _, num_points = self.point_decode(xyzs, None, code, density_only=True, **kwargs)
         return sigmas, num_points
 
+    def visualize(self, code, scene_name, viz_dir, code_range=[-1, 1], level=6):
+        """``scene_<name>.png`` per scene under ``viz_dir``: the three planes of ``code`` (S, 3, C, h, w) as one viridis image of 3 h rows and C w
+        columns, rows reversed within each plane unless ``flip_z`` (triplane_decoder.py:186-194; ``viz.write_code_planes``).  ``level`` (extra):
+        the files' deflate level."""
+        from .viz import write_code_planes
+        return write_code_planes(viz_dir, code, scene_name, code_range=code_range, flip_z=self.flip_z, level=level)
+
     # ------------------------------------------------------------------------------ fused eval render
     def _forward_eval_fused(self, rays_o, rays_d, code, density_bitfield, grid_size, dt_gamma, T_thresh, bg_color):
         planes = pack_triplanes(code.detach(), self.plane_dtype)

@@ -288,14 +288,20 @@ class BaseNeRF(nn.Module):
         raise NotImplementedError("BaseNeRF has no training step of its own; MultiSceneNeRF / DiffusionNeRF do")
 
     # ---- evaluation ------------------------------------------------------------------------------------------------------------------------------
-    def _eval_test_views(self, data, decoder, code, density_bitfield):
+    def _eval_test_views(self, data, decoder, code, density_bitfield, viz_dir=None):
         """``test_poses`` rendered and quantised to k/255, and scored -> (log_vars, pred_imgs (S, V, 3, h, w) or None, extras).  As
         ``eval_and_viz`` (base_nerf.py:535-558): with ``test_imgs`` (S, V, h, w, 3) in the batch and ``test_cfg['skip_eval']`` unset, the views are
         rendered at the ground truth's size and scored against it -- ``log_vars`` holds ``test_psnr`` / ``test_ssim``, the means over all views, and
         the extras ``test_metrics``, the per-view values as (S, V) device tensors (metrics.image_metrics).  With ``use_lpips_metric`` and a net
         (``set_lpips`` / ``test_cfg['lpips_weights']``) ``test_lpips`` and ``test_metrics['lpips']`` join them (metrics.image_lpips; base_nerf.py:560-570);
-        without a net nothing is added."""
+        without a net nothing is added.
+
+        With ``viz_dir`` -- the keyword of ``val_step``, else ``test_cfg['viz_dir']`` -- the views are then written as PNG files, beside their ground truth
+        and named after their scores when the batch was scored (``viz.write_views``; base_nerf.py:576-601), and the scenes' code planes -- with
+        ``init_code``, also the mean code as scene ``000_mean`` -- by ``decoder.visualize`` with ``code_range = test_cfg['clip_range']`` ([-1, 1]);
+        ``test_cfg['viz_compress_level']`` (6) is the files' deflate level.  The batch then needs ``data['scene_name']``."""
         pred, log_vars, extra = None, dict(), dict()
+        image = target = None
         if "test_poses" in data:
             evaluate = "test_imgs" in data and not self.test_cfg.get("skip_eval", False)
             h, w = data["test_imgs"].shape[2:4] if evaluate else self.test_cfg.get("img_size", (128, 128))
@@ -312,7 +318,28 @@ class BaseNeRF(nn.Module):
                     log_vars.update(test_lpips=float(lpips.mean()))
                     extra["test_metrics"].update(lpips=lpips)
             pred = image.permute(0, 1, 4, 2, 3)
+        if viz_dir is None:
+            viz_dir = self.test_cfg.get("viz_dir", None)
+        if viz_dir is not None:
+            self._write_viz(viz_dir, data, decoder, code, image, target, extra.get("test_metrics"))
         return log_vars, pred, extra
+
+    def _write_viz(self, viz_dir, data, decoder, code, image, target, metrics):
+        """the files of ``viz_dir`` (``_eval_test_views``): ``image`` (S, V, h, w, 3) at k / 255 or None, ``target`` the scored ground truth or None"""
+        from . import viz
+        if "scene_name" not in data:
+            raise KeyError("val_step: viz_dir is set, so the batch needs data['scene_name'] (one file name per scene)")
+        names = list(data["scene_name"])
+        level = self.test_cfg.get("viz_compress_level", 6)
+        if image is not None:
+            scored = target is not None and "test_img_paths" in data        # the reference names a scored view after its image file and its scores
+            viz.write_views(viz_dir, names, image, target, img_paths=data["test_img_paths"] if scored else None, metrics=metrics if scored else None,
+                            level=level)
+        decoder = getattr(decoder, "module", decoder)                       # (a DistributedDataParallel wrapper, as base_nerf.py:602-603)
+        code_range = self.test_cfg.get("clip_range", [-1, 1])
+        decoder.visualize(code, names, viz_dir, code_range=code_range, level=level)
+        if self.init_code is not None:
+            decoder.visualize(self.init_code[None], ["000_mean"], viz_dir, code_range=code_range, level=level)
 
     def val_step(self, data, march_noises=None, density_jitters=None, **kwargs):
         """Reconstruction by optimisation, then evaluation (base_nerf.py:622-673): the batch's scene files (``data['code']``), or codes fitted to
@@ -320,7 +347,8 @@ class BaseNeRF(nn.Module):
         ``density_jitters``: injected draws, consumed in order); ``test_poses`` rendered and scored as ``_eval_test_views``.  ``log_vars`` adds
         ``train_psnr`` (the last inversion iteration's rendered rays against their targets; only when inversion ran) and ``code_rms``; with
         ``test_cfg['save_dir']`` the scenes are written by ``save_scene`` and, with ``test_cfg['save_mesh']``, their meshes by ``save_mesh``
-        (``_save_outputs``).  Returns the keys of ``DiffusionNeRF.val_step``."""
+        (``_save_outputs``); with ``viz_dir=`` (or ``test_cfg['viz_dir']``) the views and code planes are written as PNG files (``_eval_test_views``).
+        Returns the keys of ``DiffusionNeRF.val_step``."""
         decoder = self._modules_for_eval()
         rgb = target = None
         if "code" in data:
@@ -331,7 +359,7 @@ class BaseNeRF(nn.Module):
                 code, grid, bits, _, _, rgb, target = self.inverse_code(decoder, *cond.ray_args(), dt_gamma=cond.dt_gamma,
                                                                         cfg=self.test_cfg, march_noises=march_noises, density_jitters=density_jitters)
         with torch.no_grad():
-            log_vars, pred, extra = self._eval_test_views(data, decoder, code, bits)
+            log_vars, pred, extra = self._eval_test_views(data, decoder, code, bits, viz_dir=kwargs.get("viz_dir"))
             if rgb is not None:
                 log_vars.update(train_psnr=float(nerf.eval_psnr(rgb.detach(), target).mean()))
             log_vars.update(code_rms=float(code.square().flatten(1).mean().sqrt().mean()))
@@ -822,9 +850,11 @@ class DiffusionNeRF(MultiSceneNeRF):
     def val_step(self, data, **kwargs):
         """Scene codes for the batch (``_scene_from``), and its ``test_poses`` rendered, quantised to k/255 (``pred_imgs``, (S, V, 3, h, w)) and
         scored against ``test_imgs`` as ``BaseNeRF._eval_test_views`` does.  With ``test_cfg['save_dir']`` the scenes are then written by
-        ``save_scene`` and, with ``test_cfg['save_mesh']``, their meshes by ``save_mesh`` (``_save_outputs``)."""
+        ``save_scene`` and, with ``test_cfg['save_mesh']``, their meshes by ``save_mesh`` (``_save_outputs``).  ``viz_dir=`` (or
+        ``test_cfg['viz_dir']``): the views and code planes as PNG files (``_eval_test_views``)."""
+        viz_dir = kwargs.pop("viz_dir", None)
         with torch.no_grad():
             code, grid, bits = self._scene_from(data, kwargs)
-            log_vars, pred, extra = self._eval_test_views(data, self._modules_for_eval(), code, bits)
+            log_vars, pred, extra = self._eval_test_views(data, self._modules_for_eval(), code, bits, viz_dir=viz_dir)
             self._save_outputs(data, self._modules_for_eval(), code, grid, bits)
         return dict(log_vars=log_vars, num_samples=code.size(0), pred_imgs=pred, code=code, density_grid=grid, density_bitfield=bits, **extra)

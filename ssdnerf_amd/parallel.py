@@ -80,10 +80,12 @@ def weighted_log_vars(log_vars: dict, batch_sizes: List[int], device=None) -> di
     return out
 
 
-def evaluate_3d(model, batches, metrics=None, feed_batch_size=32, **sample_kwargs) -> dict:
-    """The scene-parallel evaluation loop of lib/apis/test.py:12-73, without the visualisation and the progress bar:
+def evaluate_3d(model, batches, metrics=None, feed_batch_size=32, viz_dir=None, viz_step=1, **sample_kwargs) -> dict:
+    """The scene-parallel evaluation loop of lib/apis/test.py:12-73, without the progress bar:
     ``model.val_step(data, **sample_kwargs)`` on every batch of THIS rank (``batches``: an iterable of batch dicts, e.g. this rank's data
     loader), then every logged scalar (``test_psnr``, ``test_ssim``) averaged over all scenes of all ranks by ``weighted_log_vars``.
+    With ``viz_dir``, every ``viz_step``-th batch (``i % viz_step == 0``, test.py:29-30) gets ``viz_dir=viz_dir`` and writes its views and code
+    planes as PNG files (``BaseNeRF._eval_test_views``); every rank writes its own scenes.
 
     ``metrics``: objects with ``feed(images, mode)`` / ``summary()`` / ``result_dict`` (``fidkid.FIDKID``; ``config.build_metrics``).  The rendered views
     ``out['pred_imgs']`` (S, V, 3, h, w) in [0, 1] are fed ``feed_batch_size`` at a time as ``metric.feed(batch * 2 - 1, 'fakes')``, and ``data['test_imgs']``
@@ -91,8 +93,9 @@ def evaluate_3d(model, batches, metrics=None, feed_batch_size=32, **sample_kwarg
     metric's ``summary()`` -- which reduces over the ranks itself -- joins the returned dict (``fid``, ``fid_mean``, ``fid_cov``, ``kid``)."""
     log_vars, batch_sizes = {}, []
     metrics = list(metrics) if metrics else []
-    for data in batches:
-        out = model.val_step(data, **sample_kwargs)
+    for i, data in enumerate(batches):
+        viz = dict(viz_dir=viz_dir) if viz_dir is not None and i % viz_step == 0 else {}
+        out = model.val_step(data, **viz, **sample_kwargs)
         for key, value in out["log_vars"].items():
             log_vars.setdefault(key, []).append(value)
         batch_sizes.append(out["num_samples"])
