@@ -291,6 +291,25 @@ int ssdnerf_dpmpp_step_v(const float* x_t, const float* v, const float* x0_prev,
                          float d, float e, float clip_lo, float clip_hi, float* x0_out, float* xnext_out, void* stream);
 uint32_t ssdnerf_dpmpp_block_cap(void);
 
+/* Counter-based N(0, 1): Philox4x32-10 keyed by the 64-bit seed (low word first), counter {quad index low, high, draw, 0}, 23-bit uniforms
+ * u = ((r >> 9) + 0.5) 2^-23 and Box-Muller per quad of four elements (csrc/philox.h has the definition; |z| <= 5.768).  Element i depends on
+ * (seed, draw, i) alone.  n elements (multiple of 4; 0 is a no-op). */
+int ssdnerf_philox_normal_fill(float* out, uint64_t n, uint64_t seed, uint32_t draw, void* stream);
+
+/* One noise-injecting sampling step of the latent in V-parameterisation, the noise z made in registers by the generator above (the same inline
+ * function: z is bit for bit what ssdnerf_philox_normal_fill(out, n, seed, draw) stores, and it is not stored here):
+ *   x0 = clamp(sqrt_ab * x_t - sqrt_1mab * v, lo, hi);   eps = (x_t - sqrt_ab * x0) / sqrt_1mab;
+ *   form 0 ('ddim', eta > 0):        x_next = c * x0 + d * eps + nz * z
+ *   form 1 ('langevin'):             x_next = x_t - d * eps + nz * z
+ *   form 2 ('ddpm', 'dpmpp_sde'):    x_next = c * x0 + d * x_t + e * x0_prev + nz * z     (x0_prev is read only when e != 0)
+ * n elements (multiple of 4; 0 is a no-op).  xnext_out may alias x_t and x0_out may alias v (element i is read before it is written).  A null
+ * pointer, n % 4 != 0, an unknown form, x0_prev == NULL with e != 0 and x0_out == x0_prev fail with SSDNERF_E_INVALID before any launch.
+ * ssdnerf_sde_block_cap(): the cap on the number of 256-lane blocks of both launches; larger inputs go round the grid-stride loop. */
+int ssdnerf_sde_step_v(const float* x_t, const float* v, const float* x0_prev, uint64_t n, int form, float sqrt_ab, float sqrt_1mab, float c,
+                       float d, float e, float nz, float clip_lo, float clip_hi, uint64_t seed, uint32_t draw, float* x0_out, float* xnext_out,
+                       void* stream);
+uint32_t ssdnerf_sde_block_cap(void);
+
 /* Camera rays of n_views pinhole views (get_cam_rays, lib/core/utils/nerf_utils.py:17-61): c2w [n_views][4][4] row-major,
  * intrinsics [n_views][4] = {fx, fy, cx, cy}; rays_o, rays_d [n_views][h][w][3]: pixel-centre (x + 0.5) directions rotated by
  * c2w[:3,:3] and L2-normalised, origins c2w[:3,3] broadcast. */

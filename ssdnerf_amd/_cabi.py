@@ -40,6 +40,7 @@ EXPORTS = [
     "ssdnerf_cache_max_scenes", "ssdnerf_cache_load_multi", "ssdnerf_cache_store_multi",
     "ssdnerf_dpmpp_step_v", "ssdnerf_dpmpp_block_cap",
     "ssdnerf_png_filter_rows", "ssdnerf_code_plane_rgb",
+    "ssdnerf_philox_normal_fill", "ssdnerf_sde_step_v", "ssdnerf_sde_block_cap",
 ]
 
 
@@ -129,6 +130,11 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_dpmpp_block_cap.restype = ctypes.c_uint32
         l.ssdnerf_dpmpp_block_cap.argtypes = []
         l.ssdnerf_dpmpp_step_v.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64] + [ctypes.c_float] * 7 + [ctypes.c_void_p] * 3
+        l.ssdnerf_sde_block_cap.restype = ctypes.c_uint32
+        l.ssdnerf_sde_block_cap.argtypes = []
+        l.ssdnerf_philox_normal_fill.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
+        l.ssdnerf_sde_step_v.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_int] + [ctypes.c_float] * 8 + \
+                                        [ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 3
         l.ssdnerf_png_filter_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 2
         l.ssdnerf_code_plane_rgb.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2
         if l.ssdnerf_abi_version() != ABI_VERSION:

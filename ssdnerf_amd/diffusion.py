@@ -12,6 +12,11 @@ methods are the reference's; the implementation is organised for the MI355X inst
   session's input buffer.  Three launches per step, no copies, no allocation, no host sync in the loop.
 * ``sample_method='dpmpp_2m'`` (not in the reference, opt-in): DPM-Solver++(2M) over the same timesteps -- the same evaluation per step, and a fused update
   (``ssdnerf_dpmpp_step_v``) that also reads the x0 of the step before from one of two alternating history buffers.
+* ``sample_method='dpmpp_2m_sde'`` (not in the reference, opt-in): the stochastic form of that solver, SDE-DPM-Solver++(2M), over the same timesteps.
+* ``test_cfg['noise_source']='device'`` (opt-in; the default ``'host'`` is the seeded CPU draw described at ``_host_noise``): every noise-injecting
+  step -- DDIM with eta > 0, Langevin corrections, the ancestral sampler, ``'dpmpp_2m_sde'`` -- stays in the session and is ONE fused launch
+  (``ssdnerf_sde_step_v``) that makes its normals in registers from a counter-based generator (csrc/philox.h) keyed by ``test_cfg['noise_seed']``;
+  the tensor-expression branch takes the same normals from ``ssdnerf_philox_normal_fill``.
 * The guided step (rendering guidance, SSDNeRF's ``grad_guide_fn``) needs autograd through the UNet and the renderer; it keeps tensors in
   the graph exactly where the reference does, with the coefficients coming from the plan as Python floats.
 """
@@ -70,6 +75,27 @@ class _PinnedRing:
 def release_pinned_buffers() -> None:
     """free the pinned host staging buffers of the seeded host draws (``_host_noise``); they are re-created on demand"""
     _PinnedRing.release()
+
+
+def _require_device_latent(x: torch.Tensor) -> None:
+    if not x.is_cuda:
+        raise ValueError("noise_source='device' needs the latent on the GPU (there is no CPU path of the counter-based generator)")
+
+
+def _device_noise(like: torch.Tensor, seed: int, draw: int) -> torch.Tensor:
+    """N(0, 1) of ``like``'s shape from the counter-based generator of csrc/philox.h, made on ``like``'s device in one launch: element i of the
+    flattened tensor depends on (seed, draw, i) alone.  ``test_cfg['noise_source'] = 'device'``; there is no CPU path."""
+    _require_device_latent(like)
+    if like.numel() % 4:
+        raise ValueError(f"noise_source='device': the latent's element count must be a multiple of 4, not {like.numel()}")
+    out = torch.empty(like.shape, dtype=torch.float32, device=like.device)
+    C.check(C.lib().ssdnerf_philox_normal_fill(C.ptr(out), C.ctypes.c_uint64(out.numel()), C.ctypes.c_uint64(int(seed) & _U64), C.u32(draw),
+                                               C.stream()), "philox_normal_fill")
+    return out
+
+
+_U64 = (1 << 64) - 1
+_SDE_FORM = {"ddim": 0, "langevin": 1, "ddpm": 2, "dpmpp_sde": 2}            # ``form`` of ssdnerf_sde_step_v per plan step kind
 
 
 def _host_noise(like: torch.Tensor) -> torch.Tensor:
@@ -131,7 +157,8 @@ class PlanStep:
         kind 'ddim'     :  c x0 + d eps + n z            (c = sqrt(abar_prev), d = sqrt(1 - abar_prev - eta^2 var), n = eta sqrt(var))
         kind 'langevin' :  x_t - d eps + n z             (d = delta b / 2, n = sqrt(delta) b)
         kind 'ddpm'     :  c x0 + d x_t + n z            (posterior mean coefficients, n = sqrt(var), 0 at t = 0)
-        kind 'dpmpp'    :  c x0 + d x_t + e x0_prev      (DPM-Solver++(2M); x0_prev: the clipped x0 of the step before; see SamplingPlan)"""
+        kind 'dpmpp'    :  c x0 + d x_t + e x0_prev      (DPM-Solver++(2M); x0_prev: the clipped x0 of the step before; see SamplingPlan)
+        kind 'dpmpp_sde':  c x0 + d x_t + e x0_prev + n z   (SDE-DPM-Solver++(2M); n = 0 on the last step; see SamplingPlan)"""
     kind: str
     t: int
     a: float
@@ -140,13 +167,13 @@ class PlanStep:
     d: float
     n: float
     emit: bool            # a trajectory point of the reference's ``save_intermediates`` list (the DDIM steps, not the Langevin corrections)
-    e: float = 0.0        # weight of the previous step's x0 (kind 'dpmpp', second-order steps only)
+    e: float = 0.0        # weight of the previous step's x0 (kinds 'dpmpp' and 'dpmpp_sde', second-order steps only)
 
 
 class SamplingPlan:
     """The whole trajectory of ``ddim_sample`` / ``ddpm_sample`` / ``dpmpp_2m_sample`` as a list of ``PlanStep``s (timesteps arange(T-1, -1,
     -T/n).long(): 50 -> 999, 979, ..., 19; 75 -> 999, 985, 972, ..., 12; the last DDIM step lands on alpha_bar_prev[0] = 1, i.e. x_prev = x0
-    exactly, and so does the last step of 'dpmpp_2m').  ``solver_order`` (1 or 2) belongs to 'dpmpp_2m' alone."""
+    exactly, and so does the last step of 'dpmpp_2m' and 'dpmpp_2m_sde').  ``solver_order`` (1 or 2) belongs to those two alone."""
 
     def __init__(self, sched: NoiseSchedule, method: str, n: int, eta: float = 0.0, langevin_steps: int = 0, langevin_delta: float = 0.1,
                  langevin_t_range: Sequence[float] = (0, 1000), var_mode: str = "FIXED_LARGE", solver_order: int = 2):
@@ -200,6 +227,34 @@ class SamplingPlan:
                     r = h_before / h
                     c, e = base * (1 + 1 / (2 * r)), -base / (2 * r)
                 steps.append(PlanStep("dpmpp", t, float(sa[t]), float(sb[t]), float(c), float(sb[t_prev] / sb[t]), 0.0, True, float(e)))
+                h_before = h
+        elif method == "dpmpp_2m_sde":
+            # SDE-DPM-Solver++(2M) (Lu et al. 2022, the stochastic multistep form): the reverse SDE contracts x_t twice as fast as the ODE and the
+            # difference comes back as fresh noise.  With h as above,
+            #   x_prev = (b_prev / b_t) e^-h x_t + a_prev (1 - e^-2h) D + b_prev sqrt(1 - e^-2h) z,       D as in 'dpmpp_2m'.
+            # d^2 b_t^2 + n^2 = b_prev^2 (the noise level lands on the schedule) and c + e + d a_t = a_prev (so does the signal).  The first-order step
+            # IS the DDIM step with sigma^2 = (b_prev / b_t)^2 (1 - a_t^2 / a_prev^2), i.e. eta = 1.  Same timesteps, one network evaluation each.
+            if solver_order not in (1, 2):
+                raise ValueError(f"dpmpp_2m_sde: solver_order must be 1 or 2, not {solver_order!r}")
+            if langevin_steps > 0:
+                raise ValueError("dpmpp_2m_sde: Langevin corrections move x_t between the two history points of a multistep update (langevin_steps must be 0)")
+            if eta != 0:
+                raise ValueError("dpmpp_2m_sde has no eta: its noise level is the solver's own (eta must be 0)")
+            lam = np.log(sa) - np.log(sb)
+            h_before = None
+            for i, t in enumerate(ts):
+                if i + 1 == len(ts):                                         # t_prev = -1: h = inf: x_prev = x0 exactly, no noise
+                    steps.append(PlanStep("dpmpp_sde", t, float(sa[t]), float(sb[t]), 1.0, 0.0, 0.0, True, 0.0))
+                    break
+                t_prev = ts[i + 1]
+                h = lam[t_prev] - lam[t]
+                base = sa[t_prev] * -np.expm1(-2 * h)
+                c, e = base, 0.0
+                if solver_order == 2 and h_before is not None:
+                    r = h_before / h
+                    c, e = base * (1 + 1 / (2 * r)), -base / (2 * r)
+                steps.append(PlanStep("dpmpp_sde", t, float(sa[t]), float(sb[t]), float(c), float(sb[t_prev] / sb[t] * np.exp(-h)),
+                                      float(sb[t_prev] * np.sqrt(-np.expm1(-2 * h))), True, float(e)))
                 h_before = h
         else:
             raise AttributeError(f"Cannot find sample method [{method}_sample] correspond to [{method}].")
@@ -432,19 +487,40 @@ class GaussianDiffusion(nn.Module):
         return x0, out
 
     # ------------------------------------------------------------------------------------------ sampling
-    def _advance(self, s: PlanStep, x_t, x0, noise=None, x0_prev=None):
-        """the latent after plan step ``s`` (see PlanStep)"""
+    def _advance(self, s: PlanStep, x_t, x0, noise=None, x0_prev=None, host_draw=True):
+        """the latent after plan step ``s`` (see PlanStep).  ``host_draw`` False (device noise): a step whose ``noise`` is None adds none."""
         if s.kind == "dpmpp":
             x = s.c * x0 + s.d * x_t
             return x + s.e * x0_prev if s.e != 0 else x
-        if s.kind == "ddpm":
+        if s.kind == "dpmpp_sde":
+            x = s.c * x0 + s.d * x_t
+            if s.e != 0:
+                x = x + s.e * x0_prev
+        elif s.kind == "ddpm":
             x = s.c * x0 + s.d * x_t
         else:
             eps = (x_t - s.a * x0) / s.b
             x = s.c * x0 + s.d * eps if s.kind == "ddim" else x_t - s.d * eps
         if s.n != 0 or s.kind == "ddpm":                                     # (the ancestral sampler draws at t = 0 too and multiplies by 0)
+            if noise is None and not host_draw:
+                return x
             x = x + s.n * (_host_noise(x_t) if noise is None else noise)
         return x
+
+    def _noise_source(self, cfg, x_t):
+        """(device mode?, seed) of one sampling call.  Device mode without ``noise_seed``: ONE draw of 64 bits from torch's default CPU generator, so
+        ``torch.manual_seed`` still reproduces the run."""
+        source = cfg.get("noise_source", "host")
+        if source not in ("host", "device"):
+            raise ValueError(f"test_cfg['noise_source'] must be 'host' or 'device', not {source!r}")
+        if source == "host":
+            return False, 0
+        _require_device_latent(x_t)
+        seed = cfg.get("noise_seed")
+        if seed is None:
+            lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+            seed = (hi << 32) | lo
+        return True, int(seed) & _U64
 
     def _fused_ok(self, x_t, cfg, grad_guide_fn, concat_cond):
         return (self.use_fused_step and grad_guide_fn is None and concat_cond is None and self.denoising_mean_mode.upper() == "V" and x_t.is_cuda
@@ -453,6 +529,8 @@ class GaussianDiffusion(nn.Module):
     def _run_plan(self, plan: SamplingPlan, noise, concat_cond=None, save_intermediates=False, grad_guide_fn=None, **kwargs):
         cfg = self.test_cfg
         x_t = noise
+        device_noise, seed = self._noise_source(cfg, x_t)
+        draw = 0                                                             # device mode: draws are numbered in plan order; a step with n == 0 consumes none
         B = x_t.size(0)
         kept: Optional[list] = [] if save_intermediates else None
         t_rows = torch.tensor([s.t for s in plan], dtype=torch.long).to(x_t.device)[:, None].expand(-1, B).contiguous()   # ONE upload for the loop
@@ -493,14 +571,44 @@ class GaussianDiffusion(nn.Module):
                 if kept is not None:
                     pending_x0 = x0.clone()                                  # (the buffer is written again two steps on)
                 continue
+            if session is not None and device_noise:
+                # ---- device-resident step of any other kind (eta > 0, Langevin, ancestral, dpmpp_sde): as above, the normals made in registers by the
+                # update itself.  A step that injects no noise keeps the deterministic kernel and consumes no draw index.
+                session.t.copy_(t_rows[i])
+                v = session.run()
+                prev = None
+                if s.kind == "dpmpp_sde":
+                    if history is None:
+                        history = [torch.empty_like(session.x), torch.empty_like(session.x)]
+                    x0, prev = history[i & 1], (history[(i & 1) ^ 1] if s.e != 0 else None)
+                else:
+                    x0 = torch.empty_like(session.x) if kept is not None and s.emit else session.y
+                if s.n == 0 and _SDE_FORM[s.kind] == 2:
+                    C.check(C.lib().ssdnerf_dpmpp_step_v(C.ptr(session.x), C.ptr(v), C.ptr(prev), C.ctypes.c_uint64(v.numel()), C.f32(s.a), C.f32(s.b),
+                                                         C.f32(s.c), C.f32(s.d), C.f32(s.e), C.f32(clip[0]), C.f32(clip[1]), C.ptr(x0), C.ptr(session.x),
+                                                         C.stream()), "dpmpp_step_v")
+                else:
+                    C.check(C.lib().ssdnerf_sde_step_v(C.ptr(session.x), C.ptr(v), C.ptr(prev), C.ctypes.c_uint64(v.numel()), _SDE_FORM[s.kind],
+                                                       C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d), C.f32(s.e), C.f32(s.n), C.f32(clip[0]),
+                                                       C.f32(clip[1]), C.ctypes.c_uint64(seed), C.u32(draw), C.ptr(x0), C.ptr(session.x), C.stream()),
+                            "sde_step_v")
+                    draw += s.n != 0
+                if kept is not None and s.emit:
+                    pending_x0 = x0.clone() if s.kind == "dpmpp_sde" else x0
+                continue
             if session is not None:                                          # a step kind the fused form does not cover: leave the session
                 x_t, session = session.x.clone(), None
             # a step that injects noise (Langevin, ancestral DDPM, eta > 0): the HOST draw first -- the device still has the previous step's work queued, the
             # draw (4.8 ms for 8 cars latents) hides under it; same generator, same order of draws as drawing inside _advance
-            step_noise = _host_noise(x_t) if (s.n != 0 or s.kind == "ddpm") else None
+            if device_noise:                                                 # the same normals as the fused step's: (seed, draw, element index)
+                step_noise = _device_noise(x_t, seed, draw) if s.n != 0 else None
+                draw += s.n != 0
+            else:
+                step_noise = _host_noise(x_t) if (s.n != 0 or s.kind == "ddpm") else None
             x0, _ = self.pred_x_0(x_t, t_rows[i], grad_guide_fn=grad_guide_fn, concat_cond=cond, cfg=cfg, **kwargs)
-            x_t = self._advance(s, x_t.detach() if grad_guide_fn is not None else x_t, x0, noise=step_noise, x0_prev=x0_prev)
-            if s.kind == "dpmpp":
+            x_t = self._advance(s, x_t.detach() if grad_guide_fn is not None else x_t, x0, noise=step_noise, x0_prev=x0_prev,
+                                host_draw=not device_noise)
+            if s.kind in ("dpmpp", "dpmpp_sde"):
                 x0_prev = x0                                                 # (with guidance: the guided, clipped x0 that pred_x_0 returned)
             if kept is not None and s.emit:
                 pending_x0 = x0
@@ -522,22 +630,35 @@ class GaussianDiffusion(nn.Module):
         from the last two x0.  ``test_cfg['solver_order']`` 1 gives DDIM's own trajectory."""
         return self._run_plan(self.sampling_plan("dpmpp_2m"), noise, concat_cond, save_intermediates, **kwargs)
 
+    def dpmpp_2m_sde_sample(self, noise, show_pbar=False, concat_cond=None, save_intermediates=False, **kwargs):
+        """SDE-DPM-Solver++(2M) over the DDIM timesteps (not in the reference; opt in with ``test_cfg['sample_method'] = 'dpmpp_2m_sde'`` or the
+        constructor's ``sample_method``): ``dpmpp_2m_sample``'s evaluation, clipping, guidance hook and history, with the solver's own noise added on
+        every step but the last.  ``test_cfg['noise_source']`` decides where that noise comes from, as for every stochastic sampler here."""
+        return self._run_plan(self.sampling_plan("dpmpp_2m_sde"), noise, concat_cond, save_intermediates, **kwargs)
+
     # single-step entry points of the reference API (each resolves its coefficients like one plan entry)
-    def p_sample_ddim(self, x_t, t, t_prev, noise=None, cfg=dict(), grad_guide_fn=None, **kwargs):
+    def p_sample_ddim(self, x_t, t, t_prev, noise=None, cfg=dict(), grad_guide_fn=None, noise_seed=None, noise_draw=0, **kwargs):
+        """``noise_seed`` (extra, with ``noise_draw``; also on the two entry points below): without ``noise``, take it from the device generator
+        instead of the host draw"""
         t, t_prev, eta = int(t), int(t_prev), cfg.get("eta", 0)
         sc = self.schedule
         ab_prev = sc["alphas_bar"][t_prev] if t_prev >= 0 else sc["alphas_bar_prev"][0]
         s = PlanStep("ddim", t, float(sc["sqrt_alphas_bar"][t]), float(sc["sqrt_one_minus_alphas_bar"][t]), float(np.sqrt(ab_prev)),
                      float(np.sqrt(1 - ab_prev - sc["tilde_betas_t"][t] * eta ** 2)), float(eta * np.sqrt(sc["tilde_betas_t"][t])), True)
         x0, _ = self.pred_x_0(x_t, t, grad_guide_fn=grad_guide_fn, cfg=cfg, **kwargs)
-        return self._advance(s, x_t, x0, noise), x0
+        return self._advance(s, x_t, x0, self._seeded(s, x_t, noise, noise_seed, noise_draw)), x0
 
-    def p_sample_langevin(self, x_t, t, noise=None, cfg=dict(), grad_guide_fn=None, **kwargs):
+    def _seeded(self, s, x_t, noise, noise_seed, noise_draw):
+        if noise is None and noise_seed is not None and (s.n != 0 or s.kind == "ddpm"):
+            return _device_noise(x_t, noise_seed, noise_draw)
+        return noise
+
+    def p_sample_langevin(self, x_t, t, noise=None, cfg=dict(), grad_guide_fn=None, noise_seed=None, noise_draw=0, **kwargs):
         t, delta = int(t), cfg.get("langevin_delta", 0.1)
         sigma = float(self.schedule["sqrt_one_minus_alphas_bar"][t])
         s = PlanStep("langevin", t, float(self.schedule["sqrt_alphas_bar"][t]), sigma, 0.0, 0.5 * delta * sigma, math.sqrt(delta) * sigma, False)
         x0, _ = self.pred_x_0(x_t, t, grad_guide_fn=grad_guide_fn, cfg=cfg, **kwargs)
-        return self._advance(s, x_t, x0, noise)
+        return self._advance(s, x_t, x0, self._seeded(s, x_t, noise, noise_seed, noise_draw))
 
     def q_posterior_mean(self, x_0, x_t, t):
         idx = torch.as_tensor(t).reshape(-1).cpu().numpy()
@@ -545,18 +666,18 @@ class GaussianDiffusion(nn.Module):
         c2 = x_0.new_tensor(self.schedule["tilde_mu_t_coef2"][idx], dtype=torch.float32).reshape(-1, 1, 1, 1)
         return c1 * x_0 + c2 * x_t
 
-    def p_sample_ddpm(self, x_t, t, noise=None, cfg=dict(), grad_guide_fn=None, **kwargs):
+    def p_sample_ddpm(self, x_t, t, noise=None, cfg=dict(), grad_guide_fn=None, noise_seed=None, noise_draw=0, **kwargs):
         key = ("ddpm-every-t", self.denoising_var_mode)
         if key not in self._plans:
             self._plans[key] = SamplingPlan(self.schedule, "ddpm", self.num_timesteps, var_mode=self.denoising_var_mode)   # every t once
         s = self._plans[key].steps[self.num_timesteps - 1 - int(t)]
         x0, _ = self.pred_x_0(x_t, int(t), grad_guide_fn=grad_guide_fn, cfg=cfg, **kwargs)
-        return self._advance(s, x_t, x0, noise), x0
+        return self._advance(s, x_t, x0, self._seeded(s, x_t, noise, noise_seed, noise_draw)), x0
 
     def sample_from_noise(self, noise, **kwargs):
         name = self.test_cfg.get("sample_method", self.sample_method)       # (no config of the reference sets the test_cfg key)
         method = name.lower()
-        if method not in ("ddim", "ddpm", "dpmpp_2m"):
+        if method not in ("ddim", "ddpm", "dpmpp_2m", "dpmpp_2m_sde"):
             raise AttributeError(f"Cannot find sample method [{method}_sample] correspond to [{name}].")
         return getattr(self, f"{method}_sample")(noise=noise, **kwargs)
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """tools/bench_sample.py -- unconditional sampling end to end on one MI355X (BASELINE.json configs[3]-style workload per GPU):
-noise -> 50-step DDIM (or, --sample-method dpmpp_2m, DPM-Solver++(2M)) over the triplane latents (cars UNet, 122 M parameters) -> density grids -> V novel views per scene.
+noise -> 50-step DDIM (or, --sample-method dpmpp_2m / dpmpp_2m_sde, DPM-Solver++(2M) and its stochastic form; --eta and --noise-source for the stochastic samplers) over the triplane latents (cars UNet, 122 M parameters) -> density grids -> V novel views per scene.
 Prints one JSON line with scenes/s and the split DDIM / density / render.  Random weights, synthetic decoder: timing only."""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -13,7 +13,9 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--scenes", type=int, default=8); ap.add_argument("--views", type=int, default=251); ap.add_argument("--steps", type=int, default=50)
 ap.add_argument("--dtype", default="bf16", choices=["fp32", "bf16", "fp16"]); ap.add_argument("--reps", type=int, default=2)
 ap.add_argument("--eager-unet", action="store_true", help="module forward instead of the inference executor (the baseline this repo started from)")
-ap.add_argument("--sample-method", default="ddim", choices=["ddim", "dpmpp_2m"], help="the sampler over the same --steps timesteps (dpmpp_2m: DPM-Solver++(2M), DESIGN.md section 20)")
+ap.add_argument("--sample-method", default="ddim", choices=["ddim", "dpmpp_2m", "dpmpp_2m_sde"], help="the sampler over the same --steps timesteps (dpmpp_2m: DPM-Solver++(2M), DESIGN.md section 20; dpmpp_2m_sde: its stochastic form, section 22)")
+ap.add_argument("--noise-source", default=None, choices=["host", "device"], help="where a stochastic sampler's noise comes from (test_cfg.noise_source; unset: the key is left out, i.e. 'host')")
+ap.add_argument("--eta", type=float, default=None, help="DDIM's eta (test_cfg.eta; unset: the key is left out, i.e. 0)")
 a = ap.parse_args()
 cfg = dict(type="DiffusionNeRF", code_size=(3, 6, 128, 128), code_reshape=(18, 128, 128), code_activation=dict(type="TanhCode", scale=2), grid_size=64,
            diffusion=dict(type="GaussianDiffusion", num_timesteps=1000, betas_cfg=dict(type="linear"),
@@ -29,7 +31,8 @@ cfg = dict(type="DiffusionNeRF", code_size=(3, 6, 128, 128), code_reshape=(18, 1
            reg_loss=dict(type="RegLoss", power=2, loss_weight=3e-3), cache_size=0,
            autocast_dtype=dict(fp32=None, bf16="bfloat16", fp16="float16")[a.dtype],
            test_cfg=dict(img_size=(128, 128), num_timesteps=a.steps, clip_range=[-2, 2], density_thresh=0.1,
-                         **({} if a.sample_method == "ddim" else dict(sample_method=a.sample_method))))
+                         **({} if a.sample_method == "ddim" else dict(sample_method=a.sample_method)),
+                         **({} if a.noise_source is None else dict(noise_source=a.noise_source)), **({} if a.eta is None else dict(eta=a.eta))))
 try:
     model = MODELS.build(cfg)
 except Exception:                                   # option names differ between config generations: fall back to the minimal diffusion dict
@@ -70,6 +73,6 @@ for rep in range(a.reps + 1):                       # rep 0 = warm-up (graph cap
     if rep:
         res.append(dict(total_s=dt, ddim_ms=e0.elapsed_time(e1), density_ms=e1.elapsed_time(e2), render_ms=e2.elapsed_time(e3)))
 best = min(res, key=lambda r: r["total_s"])
-print(json.dumps(dict(metric="scenes/s, unconditional sampling + render", value=ns / best["total_s"], unit="scenes/s", scenes=ns, views_per_scene=nv, ddim_steps=a.steps, sample_method=a.sample_method,
+print(json.dumps(dict(metric="scenes/s, unconditional sampling + render", value=ns / best["total_s"], unit="scenes/s", scenes=ns, views_per_scene=nv, ddim_steps=a.steps, sample_method=a.sample_method, noise_source=a.noise_source or "host", eta=a.eta or 0.0,
                       unet_dtype=a.dtype, unet_path="eager module" if a.eager_unet else "inference executor", **{k: round(v, 2) for k, v in best.items()},
                       ms_per_ddim_step=round(best["ddim_ms"] / a.steps, 3), image_finite=bool(torch.isfinite(image).all()))))
