@@ -274,19 +274,25 @@ int ssdnerf_density_grid_update(const void* planes, int planes_dtype, uint32_t H
 int ssdnerf_packbits_dev_thresh(const void* grid, int grid_dtype, uint32_t N, const float* mean, float density_thresh,
                                 uint8_t* bitfield, void* stream);
 
-/* One DDIM step of the latent in V-parameterisation, eta = 0, no guidance (gaussian_diffusion.py:213,235,281-283):
- *   x0 = clamp(sqrt_ab * x_t - sqrt_1mab * v, lo, hi);  eps = (x_t - sqrt_ab * x0) / sqrt_1mab;
- *   x_prev = sqrt_ab_prev * x0 + dir_coef * eps,   dir_coef = sqrt(1 - ab_prev).      n elements (multiple of 4). */
+/* The sampling steps of the latent in V-parameterisation (csrc/sampler_step.hip: one kernel template behind the three step entries below).
+ * THE STEP CONTRACT, common to the three:
+ *   x0 = clamp(sqrt_ab * x_t - sqrt_1mab * v, clip_lo, clip_hi) goes to x0_out and, updated by the entry's formula, to the other output;
+ *   eps, where a formula uses it, is (x_t - sqrt_ab * x0) * fl(1 / sqrt_1mab); every product and sum rounds on its own, in the order written.
+ *   n elements (multiple of 4; 0 is a no-op).  The second output may alias x_t and x0_out may alias v (element i is read before it is written).
+ *   A null pointer and n % 4 != 0 fail with SSDNERF_E_INVALID, as every refusal does, before any launch; the message names the entry.
+ *   HISTORY (the entries that take x0_prev): it is read only when e != 0 and may be NULL only when e == 0; x0_out == x0_prev is refused.
+ * ssdnerf_dpmpp_block_cap() and ssdnerf_sde_block_cap() return the same number: the cap on the 256-lane blocks of every launch of this group;
+ * larger inputs go round the grid-stride loop. */
+
+/* One DDIM step, eta = 0, no guidance (gaussian_diffusion.py:213,235,281-283).  The step contract, and
+ *   x_prev = sqrt_ab_prev * x0 + dir_coef * eps,   dir_coef = sqrt(1 - ab_prev). */
 int ssdnerf_ddim_step_v(const float* x_t, const float* v, uint64_t n, float sqrt_ab, float sqrt_1mab, float sqrt_ab_prev,
                         float dir_coef, float clip_lo, float clip_hi, float* x0_out, float* xprev_out, void* stream);
 
-/* One DPM-Solver++(2M) step of the latent in V-parameterisation (Lu et al. 2022, data prediction, multistep; no counterpart in the reference):
- *   x0 = clamp(sqrt_ab * x_t - sqrt_1mab * v, lo, hi);   x_next = c * x0 + d * x_t + e * x0_prev,
+/* One DPM-Solver++(2M) step (Lu et al. 2022, data prediction, multistep; no counterpart in the reference).  The step contract with HISTORY, and
+ *   x_next = c * x0 + d * x_t + e * x0_prev,
  * with lambda = log(sqrt_ab / sqrt_1mab), h = lambda_prev - lambda_t, phi = -expm1(-h), r = h_of_the_step_before / h:
- *   d = sqrt_1mab_prev / sqrt_1mab,  c = sqrt_ab_prev phi (1 + 1/(2r)),  e = -sqrt_ab_prev phi / (2r);   first-order step: c = sqrt_ab_prev phi, e = 0.
- * n elements (multiple of 4; 0 is a no-op).  x0_prev may be NULL only when e == 0 (it is not read then).  xnext_out may alias x_t and x0_out may
- * alias v (element i is read before it is written); x0_out == x0_prev fails with SSDNERF_E_INVALID, as every refusal does, before any launch.
- * ssdnerf_dpmpp_block_cap(): the cap on the number of 256-lane blocks; larger inputs go round the grid-stride loop. */
+ *   d = sqrt_1mab_prev / sqrt_1mab,  c = sqrt_ab_prev phi (1 + 1/(2r)),  e = -sqrt_ab_prev phi / (2r);   first-order step: c = sqrt_ab_prev phi, e = 0. */
 int ssdnerf_dpmpp_step_v(const float* x_t, const float* v, const float* x0_prev, uint64_t n, float sqrt_ab, float sqrt_1mab, float c,
                          float d, float e, float clip_lo, float clip_hi, float* x0_out, float* xnext_out, void* stream);
 uint32_t ssdnerf_dpmpp_block_cap(void);
@@ -296,15 +302,12 @@ uint32_t ssdnerf_dpmpp_block_cap(void);
  * (seed, draw, i) alone.  n elements (multiple of 4; 0 is a no-op). */
 int ssdnerf_philox_normal_fill(float* out, uint64_t n, uint64_t seed, uint32_t draw, void* stream);
 
-/* One noise-injecting sampling step of the latent in V-parameterisation, the noise z made in registers by the generator above (the same inline
- * function: z is bit for bit what ssdnerf_philox_normal_fill(out, n, seed, draw) stores, and it is not stored here):
- *   x0 = clamp(sqrt_ab * x_t - sqrt_1mab * v, lo, hi);   eps = (x_t - sqrt_ab * x0) / sqrt_1mab;
+/* One noise-injecting step, the noise z made in registers by the generator above (the same inline function: z is bit for bit what
+ * ssdnerf_philox_normal_fill(out, n, seed, draw) stores, and it is not stored here).  The step contract with HISTORY, and
  *   form 0 ('ddim', eta > 0):        x_next = c * x0 + d * eps + nz * z
  *   form 1 ('langevin'):             x_next = x_t - d * eps + nz * z
- *   form 2 ('ddpm', 'dpmpp_sde'):    x_next = c * x0 + d * x_t + e * x0_prev + nz * z     (x0_prev is read only when e != 0)
- * n elements (multiple of 4; 0 is a no-op).  xnext_out may alias x_t and x0_out may alias v (element i is read before it is written).  A null
- * pointer, n % 4 != 0, an unknown form, x0_prev == NULL with e != 0 and x0_out == x0_prev fail with SSDNERF_E_INVALID before any launch.
- * ssdnerf_sde_block_cap(): the cap on the number of 256-lane blocks of both launches; larger inputs go round the grid-stride loop. */
+ *   form 2 ('ddpm', 'dpmpp_sde'):    x_next = c * x0 + d * x_t + e * x0_prev + nz * z
+ * An unknown form is refused. */
 int ssdnerf_sde_step_v(const float* x_t, const float* v, const float* x0_prev, uint64_t n, int form, float sqrt_ab, float sqrt_1mab, float c,
                        float d, float e, float nz, float clip_lo, float clip_hi, uint64_t seed, uint32_t draw, float* x0_out, float* xnext_out,
                        void* stream);

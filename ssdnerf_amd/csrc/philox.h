@@ -1,4 +1,4 @@
-// ssdnerf_amd/csrc/philox.h -- the counter-based normal generator of the stochastic sampling steps (sde_step.hip).
+// ssdnerf_amd/csrc/philox.h -- the counter-based normal generator of the stochastic sampling steps (sampler_step.hip).
 //
 // Integer stream: Philox4x32-10 (Salmon et al. 2011, Random123) with the standard constants.  The key is the 64-bit seed, low word first.  The counter is
 //     c0, c1   the low and high 32 bits of the quad index i4 (element i of the flattened latent belongs to quad i / 4)

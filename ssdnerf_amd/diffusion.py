@@ -7,16 +7,15 @@ methods are the reference's; the implementation is organised for the MI355X inst
   ``SamplingPlan`` -- a flat list of network evaluations, each with its timestep and its scalar coefficients.  The loops below never index
   a numpy table with a device tensor (the reference does, which costs a device->host sync per lookup, gaussian_diffusion.py:275-283) and
   never upload a table per call.
-* An unguided DDIM step is: write ``t`` into the UNet session's static buffer, replay the captured forward (``unet_fast.UnetSession``), ONE
-  fused elementwise launch (``ssdnerf_ddim_step_v``) that turns (x_t, v) into (x0, x_prev) and writes x_prev back IN PLACE into the
-  session's input buffer.  Three launches per step, no copies, no allocation, no host sync in the loop.
-* ``sample_method='dpmpp_2m'`` (not in the reference, opt-in): DPM-Solver++(2M) over the same timesteps -- the same evaluation per step, and a fused update
-  (``ssdnerf_dpmpp_step_v``) that also reads the x0 of the step before from one of two alternating history buffers.
-* ``sample_method='dpmpp_2m_sde'`` (not in the reference, opt-in): the stochastic form of that solver, SDE-DPM-Solver++(2M), over the same timesteps.
+* A step without guidance is: write ``t`` into the UNet session's static buffer, replay the captured forward (``unet_fast.UnetSession``), ONE
+  fused elementwise launch (csrc/sampler_step.hip) that turns (x_t, v) into (x0, x_next) and writes x_next back IN PLACE into the session's
+  input buffer.  Three launches per step, no copies, no allocation, no host sync in the loop.  ``ssdnerf_ddim_step_v`` serves DDIM at eta = 0;
+  ``ssdnerf_dpmpp_step_v`` serves ``sample_method='dpmpp_2m'`` (DPM-Solver++(2M) over the same timesteps; not in the reference, opt-in), which
+  also reads the x0 of the step before from one of two alternating history buffers.
 * ``test_cfg['noise_source']='device'`` (opt-in; the default ``'host'`` is the seeded CPU draw described at ``_host_noise``): every noise-injecting
-  step -- DDIM with eta > 0, Langevin corrections, the ancestral sampler, ``'dpmpp_2m_sde'`` -- stays in the session and is ONE fused launch
-  (``ssdnerf_sde_step_v``) that makes its normals in registers from a counter-based generator (csrc/philox.h) keyed by ``test_cfg['noise_seed']``;
-  the tensor-expression branch takes the same normals from ``ssdnerf_philox_normal_fill``.
+  step -- DDIM with eta > 0, Langevin corrections, the ancestral sampler, ``sample_method='dpmpp_2m_sde'`` (SDE-DPM-Solver++(2M); not in the
+  reference, opt-in) -- stays in the session too: ``ssdnerf_sde_step_v`` makes its normals in registers from a counter-based generator
+  (csrc/philox.h) keyed by ``test_cfg['noise_seed']``; the tensor-expression branch takes the same normals from ``ssdnerf_philox_normal_fill``.
 * The guided step (rendering guidance, SSDNeRF's ``grad_guide_fn``) needs autograd through the UNet and the renderer; it keeps tensors in
   the graph exactly where the reference does, with the coefficients coming from the plan as Python floats.
 """
@@ -95,7 +94,7 @@ def _device_noise(like: torch.Tensor, seed: int, draw: int) -> torch.Tensor:
 
 
 _U64 = (1 << 64) - 1
-_SDE_FORM = {"ddim": 0, "langevin": 1, "ddpm": 2, "dpmpp_sde": 2}            # ``form`` of ssdnerf_sde_step_v per plan step kind
+_SDE_FORM = {"ddim": 0, "langevin": 1, "ddpm": 2, "dpmpp": 2, "dpmpp_sde": 2}   # ``form`` of ssdnerf_sde_step_v per plan step kind
 
 
 def _host_noise(like: torch.Tensor) -> torch.Tensor:
@@ -170,6 +169,20 @@ class PlanStep:
     e: float = 0.0        # weight of the previous step's x0 (kinds 'dpmpp' and 'dpmpp_sde', second-order steps only)
 
 
+def _ddim_step(sched: NoiseSchedule, t: int, t_prev: int, eta: float) -> PlanStep:
+    """the 'ddim' step from ``t`` to ``t_prev`` (-1: past the last timestep, alpha_bar_prev[0] = 1)"""
+    ab_prev = sched["alphas_bar"][t_prev] if t_prev >= 0 else sched["alphas_bar_prev"][0]
+    var = sched["tilde_betas_t"][t]
+    return PlanStep("ddim", t, float(sched["sqrt_alphas_bar"][t]), float(sched["sqrt_one_minus_alphas_bar"][t]), float(np.sqrt(ab_prev)),
+                    float(np.sqrt(1 - ab_prev - var * eta ** 2)), float(eta * np.sqrt(var)), True)
+
+
+def _langevin_step(sched: NoiseSchedule, t: int, delta: float) -> PlanStep:
+    """one 'langevin' correction at ``t``"""
+    sigma = float(sched["sqrt_one_minus_alphas_bar"][t])
+    return PlanStep("langevin", t, float(sched["sqrt_alphas_bar"][t]), sigma, 0.0, 0.5 * delta * sigma, math.sqrt(delta) * sigma, False)
+
+
 class SamplingPlan:
     """The whole trajectory of ``ddim_sample`` / ``ddpm_sample`` / ``dpmpp_2m_sample`` as a list of ``PlanStep``s (timesteps arange(T-1, -1,
     -T/n).long(): 50 -> 999, 979, ..., 19; 75 -> 999, 985, 972, ..., 12; the last DDIM step lands on alpha_bar_prev[0] = 1, i.e. x_prev = x0
@@ -180,18 +193,14 @@ class SamplingPlan:
         T = sched.T
         self.timesteps = torch.arange(start=T - 1, end=-1, step=-(T / n)).long()
         ts = self.timesteps.tolist()
-        ab, sa, sb, var = sched["alphas_bar"], sched["sqrt_alphas_bar"], sched["sqrt_one_minus_alphas_bar"], sched["tilde_betas_t"]
+        sa, sb, var = sched["sqrt_alphas_bar"], sched["sqrt_one_minus_alphas_bar"], sched["tilde_betas_t"]
         steps: List[PlanStep] = []
         if method == "ddim":
             for i, t in enumerate(ts):
                 t_prev = ts[i + 1] if i + 1 < len(ts) else -1
-                ab_prev = ab[t_prev] if t_prev >= 0 else sched["alphas_bar_prev"][0]
-                steps.append(PlanStep("ddim", t, float(sa[t]), float(sb[t]), float(np.sqrt(ab_prev)),
-                                      float(np.sqrt(1 - ab_prev - var[t] * eta ** 2)), float(eta * np.sqrt(var[t])), True))
+                steps.append(_ddim_step(sched, t, t_prev, eta))
                 if langevin_steps > 0 and langevin_t_range[0] < t_prev < langevin_t_range[1]:
-                    sigma = float(sb[t_prev])
-                    steps += [PlanStep("langevin", t_prev, float(sa[t_prev]), sigma, 0.0, 0.5 * langevin_delta * sigma,
-                                       math.sqrt(langevin_delta) * sigma, False)] * langevin_steps
+                    steps += [_langevin_step(sched, t_prev, langevin_delta)] * langevin_steps
         elif method == "ddpm":
             mode = var_mode.upper()
             if mode == "FIXED_LARGE":
@@ -203,58 +212,41 @@ class SamplingPlan:
             for t in ts:
                 steps.append(PlanStep("ddpm", t, float(sa[t]), float(sb[t]), float(sched["tilde_mu_t_coef1"][t]), float(sched["tilde_mu_t_coef2"][t]),
                                       float(np.sqrt(table[t])) if t != 0 else 0.0, True))
-        elif method == "dpmpp_2m":
+        elif method in ("dpmpp_2m", "dpmpp_2m_sde"):
             # DPM-Solver++(2M) (Lu et al. 2022, data prediction): with lambda = log a - log b, h = lambda_prev - lambda_t, phi = -expm1(-h),
             #   x_prev = (b_prev / b_t) x_t + a_prev phi D,    D = x0 (first order)  or  (1 + 1/(2r)) x0 - (1/(2r)) x0_prev,  r = h_before / h.
             # The first-order step IS the eta = 0 DDIM step: a_prev phi = a_prev - b_prev a_t / b_t.  Same timesteps, one network evaluation each.
+            # SDE-DPM-Solver++(2M) (the stochastic multistep form): the reverse SDE contracts x_t twice as fast as the ODE and the difference comes
+            # back as fresh noise,
+            #   x_prev = (b_prev / b_t) e^-h x_t + a_prev (1 - e^-2h) D + b_prev sqrt(1 - e^-2h) z,       D as above.
+            # d^2 b_t^2 + n^2 = b_prev^2 (the noise level lands on the schedule) and c + e + d a_t = a_prev (so does the signal).  Its first-order step
+            # IS the DDIM step with sigma^2 = (b_prev / b_t)^2 (1 - a_t^2 / a_prev^2), i.e. eta = 1.
+            sde = method == "dpmpp_2m_sde"
+            kind = "dpmpp_sde" if sde else "dpmpp"
             if solver_order not in (1, 2):
-                raise ValueError(f"dpmpp_2m: solver_order must be 1 or 2, not {solver_order!r}")
+                raise ValueError(f"{method}: solver_order must be 1 or 2, not {solver_order!r}")
             if langevin_steps > 0:
-                raise ValueError("dpmpp_2m: Langevin corrections move x_t between the two history points of a multistep update (langevin_steps must be 0)")
+                raise ValueError(f"{method}: Langevin corrections move x_t between the two history points of a multistep update (langevin_steps must be 0)")
             if eta != 0:
-                raise ValueError("dpmpp_2m is the deterministic solver (eta must be 0)")
+                reason = "has no eta: its noise level is the solver's own" if sde else "is the deterministic solver"
+                raise ValueError(f"{method} {reason} (eta must be 0)")
             lam = np.log(sa) - np.log(sb)
             h_before = None
             for i, t in enumerate(ts):
-                if i + 1 == len(ts):                                         # t_prev = -1: abar_prev = 1, lambda_prev = inf, phi = 1: x_prev = x0 exactly
-                    steps.append(PlanStep("dpmpp", t, float(sa[t]), float(sb[t]), 1.0, 0.0, 0.0, True, 0.0))
+                if i + 1 == len(ts):                                         # t_prev = -1: abar_prev = 1, lambda_prev = inf, phi = 1: x_prev = x0 exactly, no noise
+                    steps.append(PlanStep(kind, t, float(sa[t]), float(sb[t]), 1.0, 0.0, 0.0, True, 0.0))
                     break
                 t_prev = ts[i + 1]
                 h = lam[t_prev] - lam[t]
-                base = sa[t_prev] * -np.expm1(-h)
+                base = sa[t_prev] * -np.expm1(-2 * h if sde else -h)
                 c, e = base, 0.0
                 if solver_order == 2 and h_before is not None:
                     r = h_before / h
                     c, e = base * (1 + 1 / (2 * r)), -base / (2 * r)
-                steps.append(PlanStep("dpmpp", t, float(sa[t]), float(sb[t]), float(c), float(sb[t_prev] / sb[t]), 0.0, True, float(e)))
-                h_before = h
-        elif method == "dpmpp_2m_sde":
-            # SDE-DPM-Solver++(2M) (Lu et al. 2022, the stochastic multistep form): the reverse SDE contracts x_t twice as fast as the ODE and the
-            # difference comes back as fresh noise.  With h as above,
-            #   x_prev = (b_prev / b_t) e^-h x_t + a_prev (1 - e^-2h) D + b_prev sqrt(1 - e^-2h) z,       D as in 'dpmpp_2m'.
-            # d^2 b_t^2 + n^2 = b_prev^2 (the noise level lands on the schedule) and c + e + d a_t = a_prev (so does the signal).  The first-order step
-            # IS the DDIM step with sigma^2 = (b_prev / b_t)^2 (1 - a_t^2 / a_prev^2), i.e. eta = 1.  Same timesteps, one network evaluation each.
-            if solver_order not in (1, 2):
-                raise ValueError(f"dpmpp_2m_sde: solver_order must be 1 or 2, not {solver_order!r}")
-            if langevin_steps > 0:
-                raise ValueError("dpmpp_2m_sde: Langevin corrections move x_t between the two history points of a multistep update (langevin_steps must be 0)")
-            if eta != 0:
-                raise ValueError("dpmpp_2m_sde has no eta: its noise level is the solver's own (eta must be 0)")
-            lam = np.log(sa) - np.log(sb)
-            h_before = None
-            for i, t in enumerate(ts):
-                if i + 1 == len(ts):                                         # t_prev = -1: h = inf: x_prev = x0 exactly, no noise
-                    steps.append(PlanStep("dpmpp_sde", t, float(sa[t]), float(sb[t]), 1.0, 0.0, 0.0, True, 0.0))
-                    break
-                t_prev = ts[i + 1]
-                h = lam[t_prev] - lam[t]
-                base = sa[t_prev] * -np.expm1(-2 * h)
-                c, e = base, 0.0
-                if solver_order == 2 and h_before is not None:
-                    r = h_before / h
-                    c, e = base * (1 + 1 / (2 * r)), -base / (2 * r)
-                steps.append(PlanStep("dpmpp_sde", t, float(sa[t]), float(sb[t]), float(c), float(sb[t_prev] / sb[t] * np.exp(-h)),
-                                      float(sb[t_prev] * np.sqrt(-np.expm1(-2 * h))), True, float(e)))
+                d, n_coef = sb[t_prev] / sb[t], 0.0
+                if sde:
+                    d, n_coef = d * np.exp(-h), sb[t_prev] * np.sqrt(-np.expm1(-2 * h))
+                steps.append(PlanStep(kind, t, float(sa[t]), float(sb[t]), float(c), float(d), float(n_coef), True, float(e)))
                 h_before = h
         else:
             raise AttributeError(f"Cannot find sample method [{method}_sample] correspond to [{method}].")
@@ -489,15 +481,10 @@ class GaussianDiffusion(nn.Module):
     # ------------------------------------------------------------------------------------------ sampling
     def _advance(self, s: PlanStep, x_t, x0, noise=None, x0_prev=None, host_draw=True):
         """the latent after plan step ``s`` (see PlanStep).  ``host_draw`` False (device noise): a step whose ``noise`` is None adds none."""
-        if s.kind == "dpmpp":
-            x = s.c * x0 + s.d * x_t
-            return x + s.e * x0_prev if s.e != 0 else x
-        if s.kind == "dpmpp_sde":
+        if _SDE_FORM[s.kind] == 2:                                           # 'ddpm', 'dpmpp', 'dpmpp_sde' (e != 0: a second-order step of the last two)
             x = s.c * x0 + s.d * x_t
             if s.e != 0:
                 x = x + s.e * x0_prev
-        elif s.kind == "ddpm":
-            x = s.c * x0 + s.d * x_t
         else:
             eps = (x_t - s.a * x0) / s.b
             x = s.c * x0 + s.d * eps if s.kind == "ddim" else x_t - s.d * eps
@@ -540,7 +527,7 @@ class GaussianDiffusion(nn.Module):
             session = self.denoising.inference_session(x_t, t_rows[0])
             if session is not None:
                 session.x.copy_(x_t)                                         # the latent lives in the UNet's static input buffer from here on
-        history, x0_prev = None, None                                        # 'dpmpp': the two alternating x0 buffers of the fused step / the generic branch's last x0
+        history, x0_prev = None, None                                        # multistep kinds: the two alternating x0 buffers of the fused step / the generic branch's last x0
         pending_x0 = None                                                    # x0 of the last emitting (DDIM) step; its trajectory point is the latent AFTER
                                                                              # the Langevin corrections that follow it (gaussian_diffusion.py:313-326)
         for i, s in enumerate(plan):
@@ -548,53 +535,33 @@ class GaussianDiffusion(nn.Module):
             if kept is not None and s.emit and pending_x0 is not None:
                 kept += [pending_x0, session.x.clone() if session is not None else x_t]
                 pending_x0 = None
-            if session is not None and s.kind == "ddim" and s.n == 0:
-                # ---- device-resident unguided DDIM step: t -> static buffer, graph replay, one fused update written back in place
+            if session is not None and (device_noise or s.kind == "dpmpp" or (s.kind == "ddim" and s.n == 0)):
+                # ---- device-resident step: t -> static buffer, graph replay, ONE fused update written back in place.  Under device noise that is a step
+                # of any kind, its normals made in registers by the update itself; a step that injects none keeps the deterministic entry and consumes no
+                # draw index.  The multistep kinds leave x0 in one of two alternating buffers and read the other, where the step before left its own.
                 session.t.copy_(t_rows[i])
                 v = session.run()
-                x0 = torch.empty_like(session.x) if kept is not None else session.y       # (x0 is only materialised when the caller keeps it)
-                C.check(C.lib().ssdnerf_ddim_step_v(C.ptr(session.x), C.ptr(v), C.ctypes.c_uint64(v.numel()), C.f32(s.a), C.f32(s.b), C.f32(s.c),
-                                                    C.f32(s.d), C.f32(clip[0]), C.f32(clip[1]), C.ptr(x0), C.ptr(session.x), C.stream()), "ddim_step_v")
-                if kept is not None:
-                    pending_x0 = x0
-                continue
-            if session is not None and s.kind == "dpmpp":
-                # ---- device-resident DPM-Solver++(2M) step: as above, and the update also reads the x0 the step before left in the other history buffer
-                if history is None:
-                    history = [torch.empty_like(session.x), torch.empty_like(session.x)]     # allocated once per call; they alternate
-                session.t.copy_(t_rows[i])
-                v = session.run()
-                x0 = history[i & 1]
-                C.check(C.lib().ssdnerf_dpmpp_step_v(C.ptr(session.x), C.ptr(v), C.ptr(history[(i & 1) ^ 1] if s.e != 0 else None),
-                                                     C.ctypes.c_uint64(v.numel()), C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d), C.f32(s.e),
-                                                     C.f32(clip[0]), C.f32(clip[1]), C.ptr(x0), C.ptr(session.x), C.stream()), "dpmpp_step_v")
-                if kept is not None:
-                    pending_x0 = x0.clone()                                  # (the buffer is written again two steps on)
-                continue
-            if session is not None and device_noise:
-                # ---- device-resident step of any other kind (eta > 0, Langevin, ancestral, dpmpp_sde): as above, the normals made in registers by the
-                # update itself.  A step that injects no noise keeps the deterministic kernel and consumes no draw index.
-                session.t.copy_(t_rows[i])
-                v = session.run()
-                prev = None
-                if s.kind == "dpmpp_sde":
+                multistep, prev = s.kind in ("dpmpp", "dpmpp_sde"), None
+                if multistep:
                     if history is None:
-                        history = [torch.empty_like(session.x), torch.empty_like(session.x)]
+                        history = [torch.empty_like(session.x), torch.empty_like(session.x)]     # allocated once per call
                     x0, prev = history[i & 1], (history[(i & 1) ^ 1] if s.e != 0 else None)
                 else:
-                    x0 = torch.empty_like(session.x) if kept is not None and s.emit else session.y
-                if s.n == 0 and _SDE_FORM[s.kind] == 2:
-                    C.check(C.lib().ssdnerf_dpmpp_step_v(C.ptr(session.x), C.ptr(v), C.ptr(prev), C.ctypes.c_uint64(v.numel()), C.f32(s.a), C.f32(s.b),
-                                                         C.f32(s.c), C.f32(s.d), C.f32(s.e), C.f32(clip[0]), C.f32(clip[1]), C.ptr(x0), C.ptr(session.x),
-                                                         C.stream()), "dpmpp_step_v")
+                    x0 = torch.empty_like(session.x) if kept is not None and s.emit else session.y   # (x0 is only materialised when the caller keeps it)
+                x, n_el, lo, hi = C.ptr(session.x), C.ctypes.c_uint64(v.numel()), C.f32(clip[0]), C.f32(clip[1])
+                if s.kind == "ddim" and s.n == 0:
+                    C.check(C.lib().ssdnerf_ddim_step_v(x, C.ptr(v), n_el, C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d), lo, hi, C.ptr(x0), x, C.stream()),
+                            "ddim_step_v")
+                elif s.kind == "dpmpp" or (s.n == 0 and _SDE_FORM[s.kind] == 2):
+                    C.check(C.lib().ssdnerf_dpmpp_step_v(x, C.ptr(v), C.ptr(prev), n_el, C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d), C.f32(s.e), lo, hi,
+                                                         C.ptr(x0), x, C.stream()), "dpmpp_step_v")
                 else:
-                    C.check(C.lib().ssdnerf_sde_step_v(C.ptr(session.x), C.ptr(v), C.ptr(prev), C.ctypes.c_uint64(v.numel()), _SDE_FORM[s.kind],
-                                                       C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d), C.f32(s.e), C.f32(s.n), C.f32(clip[0]),
-                                                       C.f32(clip[1]), C.ctypes.c_uint64(seed), C.u32(draw), C.ptr(x0), C.ptr(session.x), C.stream()),
+                    C.check(C.lib().ssdnerf_sde_step_v(x, C.ptr(v), C.ptr(prev), n_el, _SDE_FORM[s.kind], C.f32(s.a), C.f32(s.b), C.f32(s.c), C.f32(s.d),
+                                                       C.f32(s.e), C.f32(s.n), lo, hi, C.ctypes.c_uint64(seed), C.u32(draw), C.ptr(x0), x, C.stream()),
                             "sde_step_v")
                     draw += s.n != 0
                 if kept is not None and s.emit:
-                    pending_x0 = x0.clone() if s.kind == "dpmpp_sde" else x0
+                    pending_x0 = x0.clone() if multistep else x0                 # (a history buffer is written again two steps on)
                 continue
             if session is not None:                                          # a step kind the fused form does not cover: leave the session
                 x_t, session = session.x.clone(), None
@@ -640,11 +607,8 @@ class GaussianDiffusion(nn.Module):
     def p_sample_ddim(self, x_t, t, t_prev, noise=None, cfg=dict(), grad_guide_fn=None, noise_seed=None, noise_draw=0, **kwargs):
         """``noise_seed`` (extra, with ``noise_draw``; also on the two entry points below): without ``noise``, take it from the device generator
         instead of the host draw"""
-        t, t_prev, eta = int(t), int(t_prev), cfg.get("eta", 0)
-        sc = self.schedule
-        ab_prev = sc["alphas_bar"][t_prev] if t_prev >= 0 else sc["alphas_bar_prev"][0]
-        s = PlanStep("ddim", t, float(sc["sqrt_alphas_bar"][t]), float(sc["sqrt_one_minus_alphas_bar"][t]), float(np.sqrt(ab_prev)),
-                     float(np.sqrt(1 - ab_prev - sc["tilde_betas_t"][t] * eta ** 2)), float(eta * np.sqrt(sc["tilde_betas_t"][t])), True)
+        t = int(t)
+        s = _ddim_step(self.schedule, t, int(t_prev), cfg.get("eta", 0))
         x0, _ = self.pred_x_0(x_t, t, grad_guide_fn=grad_guide_fn, cfg=cfg, **kwargs)
         return self._advance(s, x_t, x0, self._seeded(s, x_t, noise, noise_seed, noise_draw)), x0
 
@@ -654,9 +618,8 @@ class GaussianDiffusion(nn.Module):
         return noise
 
     def p_sample_langevin(self, x_t, t, noise=None, cfg=dict(), grad_guide_fn=None, noise_seed=None, noise_draw=0, **kwargs):
-        t, delta = int(t), cfg.get("langevin_delta", 0.1)
-        sigma = float(self.schedule["sqrt_one_minus_alphas_bar"][t])
-        s = PlanStep("langevin", t, float(self.schedule["sqrt_alphas_bar"][t]), sigma, 0.0, 0.5 * delta * sigma, math.sqrt(delta) * sigma, False)
+        t = int(t)
+        s = _langevin_step(self.schedule, t, cfg.get("langevin_delta", 0.1))
         x0, _ = self.pred_x_0(x_t, t, grad_guide_fn=grad_guide_fn, cfg=cfg, **kwargs)
         return self._advance(s, x_t, x0, self._seeded(s, x_t, noise, noise_seed, noise_draw))
 

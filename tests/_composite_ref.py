@@ -1,5 +1,5 @@
 """float64 references of the volume-rendering composite kernels (csrc/raymarching_ops.hip: k_composite_train_fwd, k_composite_train_bwd,
-k_composite_rays) and of the DDIM update (csrc/ddim.hip: k_ddim_step_v), with per-element error bounds derived from them, and the seeded input
+k_composite_rays) and of the DDIM update (csrc/sampler_step.hip: k_step_v, form 0 without noise), with per-element error bounds derived from them, and the seeded input
 families both test modules draw from: tests/test_composite_bounds_cpu.py (the bounds accept an fp32 emulation of each kernel and reject subtly
 wrong ones) and tests/test_composite_fp64_gpu.py (the kernels meet them).
 
@@ -240,7 +240,7 @@ def composite_rays_ref(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas
 
 # ------------------------------------------------------------------------------------------------ DDIM step
 def ddim_step_ref(x_t, v, a, b, c, d, lo, hi):
-    """k_ddim_step_v in float64, with bounds: p = clamp(a x_t - b v, lo, hi), eps = (x_t - a p) / b, x_prev = c p + d eps; the coefficients as the
+    """The DDIM step (k_step_v<0, false, false>) in float64, with bounds: p = clamp(a x_t - b v, lo, hi), eps = (x_t - a p) / b, x_prev = c p + d eps; the coefficients as the
     C floats the library receives.
       p:      two products and a subtraction (or a product and an fma), each rounding at most u times one of the two magnitudes, twice at most:
               B_p = 2 u (|a x_t| + |b v|).  The clamp is 1-Lipschitz and monotone, and lo / hi are exact: it carries B_p and needs no exclusion.

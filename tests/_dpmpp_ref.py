@@ -1,4 +1,4 @@
-"""float64 references of the DPM-Solver++(2M) sampler (ssdnerf_amd/diffusion.py: SamplingPlan 'dpmpp_2m', csrc/dpmpp.hip: k_dpmpp_step_v): the
+"""float64 references of the DPM-Solver++(2M) sampler (ssdnerf_amd/diffusion.py: SamplingPlan 'dpmpp_2m', csrc/sampler_step.hip: k_step_v, form 2 without noise): the
 kernel's update with per-element error bounds, the plan's coefficients, and an analytic denoiser whose probability-flow ODE has a closed form.
 Both test modules draw from here: tests/test_dpmpp_cpu.py (the bounds accept an fp32 emulation of the kernel and reject wrong ones; the plan; the
 sampler's generic branch) and tests/test_dpmpp_gpu.py (the kernel meets the bounds; fused against generic).
@@ -17,7 +17,7 @@ from _composite_ref import U32, _f64, check_le, f32_exact  # noqa: F401  (check_
 
 # ------------------------------------------------------------------------------------------------ the kernel
 def dpmpp_step_ref(x_t, v, q, a, b, c, d, e, lo, hi):
-    """k_dpmpp_step_v in float64, with bounds: p = clamp(a x_t - b v, lo, hi), x_next = c p + d x_t + e q (q: the x0 of the step before; ``None``
+    """The DPM-Solver++ step (k_step_v<2, HAS_PREV, false>) in float64, with bounds: p = clamp(a x_t - b v, lo, hi), x_next = c p + d x_t + e q (q: the x0 of the step before; ``None``
     stands for the NULL pointer of a first-order step and needs e == 0); the coefficients as the C floats the library receives.
       p:      two products and a subtraction (or a product and an fma), each rounding at most u times a magnitude it rounds:
               |fl(fl(a x) - fl(b v)) - (a x - b v)| <= u |a x| + u |b v| + u (1 + u) (|a x| + |b v|), so B_p = 2 u (1 + u) (|a x_t| + |b v|).

@@ -1,4 +1,4 @@
-"""References of the counter-based noise and of the stochastic sampling steps (ssdnerf_amd/csrc/philox.h, csrc/sde_step.hip; ssdnerf_amd/diffusion.py:
+"""References of the counter-based noise and of the stochastic sampling steps (ssdnerf_amd/csrc/philox.h, csrc/sampler_step.hip; ssdnerf_amd/diffusion.py:
 SamplingPlan 'dpmpp_2m_sde'): Philox4x32-10 restated in numpy, the float64 Box-Muller of its words with a per-element bound of the fp32 device
 arithmetic, the kernel's three update forms in float64 with per-element bounds, and the plan's coefficients from the alphas_bar table alone.
 Both test modules draw from here: tests/test_sde_cpu.py (known answers, the gcc build of philox.h, statistics, the bounds accept an fp32 emulation and
@@ -122,7 +122,7 @@ FORMS = {"ddim": 0, "langevin": 1, "ddpm": 2, "dpmpp_sde": 2}
 
 
 def sde_step_ref(form, x_t, v, q, z, a, b, c, d, e, nz, lo, hi):
-    """k_sde_step_v in float64, with bounds; the coefficients as the C floats the library receives, z the fp32 normals the kernel adds (exact inputs here:
+    """k_step_v (csrc/sampler_step.hip, the noise-injecting forms) in float64, with bounds; the coefficients as the C floats the library receives, z the fp32 normals the kernel adds (exact inputs here:
     their own error is ``normal_bounds``' business).  p = clamp(a x_t - b v, lo, hi), eps = (x_t - a p) / b,
         form 0:  c p + d eps + nz z         form 1:  x_t - d eps + nz z         form 2:  c p + d x_t + e q + nz z   (q None: the NULL pointer, e == 0)
       p:    as in _dpmpp_ref.dpmpp_step_ref: B_p = 2 u (1 + u) (|a x_t| + |b v|); the clamp carries it.

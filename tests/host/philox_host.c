@@ -1,4 +1,4 @@
-/* tests/host/philox_host.c -- TEST INFRASTRUCTURE.  Host build (gcc) of the integer stream the device kernels k_philox_normal_fill / k_sde_step_v
+/* tests/host/philox_host.c -- TEST INFRASTRUCTURE.  Host build (gcc) of the integer stream the device kernels k_philox_normal_fill / k_step_v
  * draw their normals from (ssdnerf_amd/csrc/philox.h). */
 #include <stddef.h>
 #include "../../ssdnerf_amd/csrc/philox.h"

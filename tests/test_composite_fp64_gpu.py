@@ -1,4 +1,4 @@
-"""The composite kernels (csrc/raymarching_ops.hip, through ``ssdnerf_amd.raymarching``) and the DDIM step (csrc/ddim.hip, through the C ABI as
+"""The composite kernels (csrc/raymarching_ops.hip, through ``ssdnerf_amd.raymarching``) and the DDIM step (csrc/sampler_step.hip, through the C ABI as
 the sampler calls it) against the float64 references and per-element bounds of tests/_composite_ref.py, on the seeded families that
 tests/test_composite_bounds_cpu.py proves the bounds on: ray ids that are not record numbers, shuffled offsets, thin and vanishing media,
 opaque samples, records past the end of the sample arrays, padding rows, ragged block tails.  Oracle parity stays in tests/test_hip_ops_gpu.py.

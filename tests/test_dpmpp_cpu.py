@@ -1,5 +1,5 @@
 """CPU tests of the DPM-Solver++(2M) sampler (``SamplingPlan`` method 'dpmpp_2m', ``GaussianDiffusion.dpmpp_2m_sample``, the generic branch of
-``_run_plan``) and of the error bounds tests/test_dpmpp_gpu.py holds csrc/dpmpp.hip to: the plan's coefficients against a float64 restatement,
+``_run_plan``) and of the error bounds tests/test_dpmpp_gpu.py holds csrc/sampler_step.hip to: the plan's coefficients against a float64 restatement,
 first order == DDIM, the bounds accept an fp32 emulation of the kernel and reject wrong ones, convergence on a prior whose probability-flow ODE
 has a closed form, guidance, refusals, and the existing plans unchanged."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The DPM-Solver++(2M) step (csrc/dpmpp.hip, through the C ABI as the sampler calls it) against the float64 reference and per-element bounds of
+"""The DPM-Solver++(2M) step (csrc/sampler_step.hip, through the C ABI as the sampler calls it) against the float64 reference and per-element bounds of
 tests/_dpmpp_ref.py (which tests/test_dpmpp_cpu.py proves on an fp32 emulation), its refusals, the fused branch of ``_run_plan`` against the
 generic one, and the sampler through ``DiffusionNeRF.val_uncond``.
 

@@ -1,7 +1,7 @@
 """CPU tests of the stochastic sampling feature: the counter-based generator (csrc/philox.h: known answers, a gcc build against the numpy restatement of
 tests/_philox_ref.py, statistics of its normals), the ``SamplingPlan`` method 'dpmpp_2m_sde' (coefficients against a float64 restatement, the two
 invariants, first order == DDIM with its own sigma, second order closer to the prior's spread than first), ``test_cfg['noise_source']`` (refusals, what
-the host generator is asked for, how draws are numbered) and the error bounds tests/test_sde_gpu.py holds csrc/sde_step.hip to (they accept an fp32
+the host generator is asked for, how draws are numbered) and the error bounds tests/test_sde_gpu.py holds csrc/sampler_step.hip to (they accept an fp32
 emulation of every form and reject wrong ones)."""
 import ctypes
 import os
@@ -330,7 +330,7 @@ def _fma(a, b, c):
 
 def _emulate(form, x, v, q, z, a, b, c, d, e, nz, lo, hi, variant="separate", wrong=None):
     """the kernel in fp32 numpy.  ``variant``: 'separate' (every product and sum rounds) or 'fma' (products fused into the sums).
-    ``wrong``: None, or one of the mistakes the bounds must catch."""
+    ``wrong``: None, or one of the mistakes the bounds must catch.  ``z`` None: a deterministic entry, no noise term at all."""
     a, b, c, d, e, nz, lo, hi = (np.float32(s) for s in (a, b, c, d, e, nz, lo, hi))
     inv_b = np.float32(1.0) / b
     if wrong == "e_sign":
@@ -355,7 +355,7 @@ def _emulate(form, x, v, q, z, a, b, c, d, e, nz, lo, hi, variant="separate", wr
             s = c * p + d * eps if sep else _fma(d, eps, c * p)
         else:
             s = x - d * eps if sep else _fma(-d, eps, x)
-    xn = s + nz * z if sep else _fma(nz, z, s)
+    xn = s if z is None else s + nz * z if sep else _fma(nz, z, s)
     if wrong == "clamp_after":
         p, xn = np.clip(p, lo, hi), np.clip(xn, lo, hi)
     return np.asarray(p, np.float32), np.asarray(xn, np.float32)

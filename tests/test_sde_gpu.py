@@ -1,4 +1,4 @@
-"""The counter-based normal fill and the fused stochastic step (csrc/philox.h, csrc/sde_step.hip, through the C ABI as the sampler calls them) against the
+"""The counter-based normal fill and the fused stochastic step (csrc/philox.h, csrc/sampler_step.hip, through the C ABI as the sampler calls them) against the
 float64 references and per-element bounds of tests/_philox_ref.py (which tests/test_sde_cpu.py proves on the restatement and on an fp32 emulation), their
 refusals, the device-noise branches of ``_run_plan`` -- fused against generic, the session kept, seeds -- the untouched host mode, and the sampler through
 ``DiffusionNeRF.val_uncond`` and a guidance closure.
@@ -17,6 +17,7 @@ import torch
 
 import _dpmpp_ref as DR
 import _philox_ref as PR
+import test_dpmpp_gpu as TD  # (its step call; the tiny UNet, its weights and the fused / generic pair of the deterministic test)
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +136,50 @@ def test_step_with_unit_noise_alone_returns_the_fill_bit_for_bit(which):
         assert torch.equal(xn.view(torch.int32), z.view(torch.int32)), (n, seed, draw)
 
 
+@pytest.mark.parametrize("which", range(6))
+def test_step_entries_equal_the_fp32_restatement_bit_for_bit(which):
+    """Every instantiation behind the three step entries (csrc/sampler_step.hip) against the kernel's own fp32 operations in the kernel's order, restated
+    in numpy float32 (test_sde_cpu._emulate, 'separate': the build's -ffp-contract=off makes every product and sum round on its own), with z the bits
+    of the fill: x0_out and the updated latent agree BIT FOR BIT -- ``ssdnerf_ddim_step_v``, ``ssdnerf_dpmpp_step_v`` with and without e,
+    ``ssdnerf_sde_step_v`` in forms 0, 1, 2 and 2 with e.  And the deterministic entries equal ``ssdnerf_sde_step_v`` with nz = 0: s + 0 z is s for
+    finite z except for the sign of a zero, so that comparison is made after adding +0.0 to both."""
+    from test_sde_cpu import _emulate
+    n = PR.sde_sizes(_cap())[which]
+    seed, draw = SEEDS[which % 2]
+    x_np, v_np, q_np = PR.sde_case(n, 7)
+    x, v, q = cu(x_np), cu(v_np), cu(q_np)
+    z, _ = fill(n, seed, draw)
+    z_np = z.cpu().numpy()
+    assert np.isfinite(z_np).all()
+    bits = lambda t: (t.cpu().numpy() if torch.is_tensor(t) else np.asarray(t, np.float32)).view(np.int32)
+    same = lambda got, want: np.array_equal(bits(got), bits(want))
+    new = lambda: (torch.full_like(x, float("nan")), torch.full_like(x, float("nan")))
+    seen = set()
+    for name, form, a, b, c, d, e, nz in PR.sde_coefficients():
+        has_q = e != 0
+        x0, xn = new()
+        run_step(x, v, q if has_q else None, form, a, b, c, d, e, nz, seed, draw, x0, xn)
+        want_p, want_xn = _emulate(form, x_np, v_np, q_np, z_np, a, b, c, d, e, nz, -1.0, 1.0)
+        assert same(x0, want_p) and same(xn, want_xn), ("sde_step_v", name, n)
+        seen.add((form, has_q, True))
+        if form == 1:                                                        # (no deterministic entry takes the Langevin form)
+            continue
+        d0, dn = new()
+        if form == 0:
+            C = _C()
+            C.check(C.lib().ssdnerf_ddim_step_v(C.ptr(x), C.ptr(v), C.ctypes.c_uint64(n), C.f32(a), C.f32(b), C.f32(c), C.f32(d), C.f32(-1.0), C.f32(1.0),
+                                                C.ptr(d0), C.ptr(dn), C.stream()), "ddim_step_v")
+        else:
+            TD.run_step(x, v, q if has_q else None, a, b, c, d, e, d0, dn)
+        want_p, want_dn = _emulate(form, x_np, v_np, q_np, None, a, b, c, d, e, 0.0, -1.0, 1.0)
+        assert same(d0, want_p) and same(dn, want_dn), ("ddim_step_v" if form == 0 else "dpmpp_step_v", name, n)
+        seen.add((form, has_q, False))
+        s0, sn = new()
+        run_step(x, v, q if has_q else None, form, a, b, c, d, e, 0.0, seed, draw, s0, sn)
+        assert same(s0, d0) and same(sn + 0.0, dn + 0.0), ("nz = 0", name, n)
+    assert seen == {(0, False, True), (1, False, True), (2, False, True), (2, True, True), (0, False, False), (2, False, False), (2, True, False)}
+
+
 def test_refusals_return_an_error_code_and_launch_nothing():
     x_np, v_np, q_np = PR.sde_case(8, 3)
     x, v, q = cu(x_np), cu(v_np), cu(q_np)
@@ -159,7 +204,6 @@ def test_refusals_return_an_error_code_and_launch_nothing():
 
 
 # ------------------------------------------------------------------------------------------------ the sampler: fused against generic, device noise
-import test_dpmpp_gpu as TD  # noqa: E402  (the tiny UNet, its weights and the fused / generic pair of the deterministic test)
 
 METHODS = {  # name -> (sampler method, test_cfg additions)
     "dpmpp_2m_sde": ("dpmpp_2m_sde", {}),
