@@ -430,6 +430,24 @@ int ssdnerf_sample_rays_u8(const uint8_t* store, uint64_t num_images, uint32_t h
                            const float* intr, uint32_t S, uint32_t V, const int64_t* inds, uint32_t R, float* rays_o, float* rays_d, float* target,
                            void* stream);
 
+/* The pixel numbers of a training ray batch made on the device (csrc/scene_store.hip, definition in csrc/keyed_perm.h; fitting.RayBatcher with
+ * index_source='device'): pi(seed, scene, draw, P) is a keyed bijection of [0, P), 1 <= P < 2^32 -- a 12-round balanced Feistel network on the
+ * smallest even-width power-of-two domain that holds P (less than 4 P values), its round keys three Philox4x32-10 blocks on (seed; scene, draw, block,
+ * tag), cycle-walked into [0, P): fewer than 4 passes per position in the mean, no index array, no sort.  The counter's tag word keeps these streams
+ * apart from the noise of ssdnerf_philox_normal_fill under equal seeds.
+ *   ssdnerf_perm_indices:  out [S][R] int64,  out[s][r] = pi(seed, s, draw, P)(start + r);  start + R <= P is required.
+ *   ssdnerf_sample_rays_perm_u8:  the arguments of ssdnerf_sample_rays_u8 with (seed, draw, start) in place of inds:  ray r of scene s is pixel
+ *     p = pi(seed, s, draw, V * h * w)(start + r), always inside the views.  The ray and the colour come from the device functions
+ *     ssdnerf_sample_rays_u8 uses, so all nine floats equal, bit for bit, what that call gives when fed the output of ssdnerf_perm_indices.
+ * One lane per ray, a block within one scene (the round keys are wave-uniform), the walk a per-lane loop.  Inputs are only read, nothing outside
+ * the S * R elements of out / the S * R * 3 elements of each output is written.  No LDS, no atomics, no host synchronisation, no allocation, no
+ * workspace.  A null pointer, S, R or P == 0 (V, h or w == 0), P >= 2^32, start + R > P, more than 2^31 - 1 blocks of 256 rays, num_images == 0 or
+ * >= 2^31, an out that is not 8-byte aligned and an output or table that is not 4-byte aligned fail with SSDNERF_E_INVALID before any HIP call. */
+int ssdnerf_perm_indices(int64_t* out, uint32_t S, uint64_t P, uint64_t start, uint32_t R, uint64_t seed, uint32_t draw, void* stream);
+int ssdnerf_sample_rays_perm_u8(const uint8_t* store, uint64_t num_images, uint32_t h, uint32_t w, const int32_t* view_image, const float* c2w,
+                                const float* intr, uint32_t S, uint32_t V, uint64_t seed, uint32_t draw, uint64_t start, uint32_t R, float* rays_o,
+                                float* rays_d, float* target, void* stream);
+
 /* The per-scene training cache ON THE DEVICE (csrc/scene_cache.hip, conversions in csrc/cache_cvt.h; scene_cache.DeviceSceneCache): what
  * MultiSceneNeRF.load_cache / save_cache move per training step -- a scene's pre-activation code, the two Adam moments of its optimizer, its
  * density grid and bitfield -- between a store of `slots` scenes and the batch buffers of a step, a whole batch in ONE launch each way.

@@ -35,7 +35,7 @@ EXPORTS = [
     "ssdnerf_lpips_input", "ssdnerf_relu_pool_nhwc", "ssdnerf_lpips_layer_workspace", "ssdnerf_lpips_layer",
     "ssdnerf_feature_moments_accumulate", "ssdnerf_kid_subset_sums_workspace", "ssdnerf_kid_subset_sums",
     "ssdnerf_adam_max_tensors", "ssdnerf_adam_step_multi",
-    "ssdnerf_gather_views_u8", "ssdnerf_sample_rays_u8",
+    "ssdnerf_gather_views_u8", "ssdnerf_sample_rays_u8", "ssdnerf_perm_indices", "ssdnerf_sample_rays_perm_u8",
     "ssdnerf_ema_chunk", "ssdnerf_ema_plan_build", "ssdnerf_ema_update_multi",
     "ssdnerf_cache_max_scenes", "ssdnerf_cache_load_multi", "ssdnerf_cache_store_multi",
     "ssdnerf_dpmpp_step_v", "ssdnerf_dpmpp_block_cap",
@@ -119,6 +119,11 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_gather_views_u8.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]
         l.ssdnerf_sample_rays_u8.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 3 + \
                                             [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4
+        l.ssdnerf_perm_indices.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64,
+                                           ctypes.c_uint32, ctypes.c_void_p]
+        l.ssdnerf_sample_rays_perm_u8.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 3 + \
+                                                 [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint32] + \
+                                                 [ctypes.c_void_p] * 4
         l.ssdnerf_ema_chunk.restype = ctypes.c_uint32
         l.ssdnerf_ema_chunk.argtypes = []
         l.ssdnerf_ema_plan_build.argtypes = [ctypes.POINTER(EmaRow), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]

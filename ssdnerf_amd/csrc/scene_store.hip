@@ -27,7 +27,15 @@
 // and intrinsics, gv_unit (below) makes the colour from the pixel's three bytes; the same two functions the dense kernels call, so all nine
 // floats are the dense path's bit for bit.  No LDS, no atomics; the pose table (S * V * 80 B) is a per-lane load that stays in cache, the
 // bytes are a random gather, 36 B are written per lane.  About 1.3 MB moves at the training batch (8 x 4096 rays): launch-bound.
+//
+// k_sample_rays_perm_u8 (ssdnerf_sample_rays_perm_u8, datasets.StoredViews.sample_permuted) is that kernel without the index array: ray r of scene s is
+// pixel pi(seed, s, draw, V h w)(start + r) of the keyed permutation of keyed_perm.h, which every lane evaluates for itself.  A
+// block belongs to ONE scene (blocks_per_scene = ceil(R / 256) blocks each), so the twelve round keys -- three Philox blocks on (seed, scene, draw) --
+// are wave-uniform; the cycle walk is a per-lane loop of < 4 passes in the mean.  The pixel found goes through the same ssd_cam_ray and gv_unit as in
+// k_sample_rays_u8, so the nine floats are that kernel's bit for bit.  k_perm_indices (ssdnerf_perm_indices) writes the same pi as int64 for the
+// consumers that index dense arrays.  No LDS, no atomics, no workspace in either.
 #include "common.h"
+#include "keyed_perm.h"
 
 #define GV_THREADS 256
 #define GV_GROUPS 2
@@ -175,5 +183,88 @@ extern "C" int ssdnerf_sample_rays_u8(const uint8_t* store, uint64_t num_images,
     hipLaunchKernelGGL(k_sample_rays_u8, dim3((uint32_t)((total + RS_THREADS - 1) / RS_THREADS)), dim3(RS_THREADS), 0, (hipStream_t)stream, store, (uint32_t)hw, w,
                        view_image, c2w, intr, V, inds, R, total, rays_o, rays_d, target);
     SSD_CHECK_LAUNCH("sample_rays_u8");
+    return SSDNERF_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the same batch with its pixels numbered on the device: p = pi(seed, s, draw, V * hw)(start + r), keyed_perm.h.  Block b of the grid is block
+// b % bps of scene b / bps: s, the round keys and h are uniform over the block, r and the walk are per lane.
+SSD_DEV bool rp_locate(uint32_t R, uint32_t bps, uint32_t& s, uint32_t& r) {
+    s = blockIdx.x / bps;
+    r = (blockIdx.x - s * bps) * RS_THREADS + threadIdx.x;
+    return r < R;
+}
+
+__global__ void __launch_bounds__(RS_THREADS) k_perm_indices(int64_t* __restrict__ out, uint32_t P, uint32_t start, uint32_t R, uint32_t bps, uint32_t hbits,
+                                                             uint64_t seed, uint32_t draw) {
+    uint32_t s, r;
+    const bool live = rp_locate(R, bps, s, r);
+    const sskp_keys keys = sskp_round_keys(seed, s, draw);
+    if (!live) return;
+    out[(uint64_t)s * R + r] = (int64_t)sskp_perm(&keys, hbits, P, start + r, nullptr);
+}
+
+__global__ void __launch_bounds__(RS_THREADS) k_sample_rays_perm_u8(const uint8_t* __restrict__ store, uint32_t hw, uint32_t w, const int32_t* __restrict__ view_image,
+                                                                    const float* __restrict__ c2w, const float* __restrict__ intr, uint32_t V, uint32_t P,
+                                                                    uint32_t start, uint32_t R, uint32_t bps, uint32_t hbits, uint64_t seed, uint32_t draw,
+                                                                    float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ target) {
+    uint32_t s, r;
+    const bool live = rp_locate(R, bps, s, r);
+    const sskp_keys keys = sskp_round_keys(seed, s, draw);
+    if (!live) return;
+    const uint32_t p = sskp_perm(&keys, hbits, P, start + r, nullptr);            // < P = V * hw: always inside the views
+    const uint32_t v = p / hw, q = p - v * hw;
+    const uint64_t cam = (uint64_t)s * V + v, i = (uint64_t)s * R + r;
+    float o[3], d[3];
+    ssd_cam_ray(c2w + cam * 16, intr + cam * 4, q % w, q / w, o, d);
+    const uint8_t* px = store + ((uint64_t)view_image[cam] * hw + q) * 3;
+    const float c0 = gv_unit(px[0]), c1 = gv_unit(px[1]), c2 = gv_unit(px[2]);
+    rays_o[3 * i + 0] = o[0]; rays_o[3 * i + 1] = o[1]; rays_o[3 * i + 2] = o[2];
+    rays_d[3 * i + 0] = d[0]; rays_d[3 * i + 1] = d[1]; rays_d[3 * i + 2] = d[2];
+    target[3 * i + 0] = c0; target[3 * i + 1] = c1; target[3 * i + 2] = c2;
+}
+
+// the checks the two entry points share; on success *bps_out is the blocks per scene and S * *bps_out fits the grid
+static int rp_check(const char* what, uint32_t S, uint64_t P, uint64_t start, uint32_t R, uint32_t* bps_out) {
+    SSD_REQUIRE(S > 0 && R > 0 && P > 0, "%s: S, R and P must be positive (S = %u, R = %u, P = %llu)", what, S, R, (unsigned long long)P);
+    SSD_REQUIRE(P < ((uint64_t)1 << 32), "%s: P = %llu, the permutation is defined below 2^32", what, (unsigned long long)P);
+    SSD_REQUIRE(start <= P && R <= P - start, "%s: positions [%llu, %llu + %u) leave [0, P = %llu)", what, (unsigned long long)start,
+                (unsigned long long)start, R, (unsigned long long)P);
+    const uint32_t bps = (R + RS_THREADS - 1) / RS_THREADS;                         // R <= P < 2^32: no overflow, bps <= 2^24
+    SSD_REQUIRE((uint64_t)S * bps <= 0x7fffffffull, "%s: S * ceil(R / %d) is more than 2^31 - 1 blocks", what, RS_THREADS);
+    *bps_out = bps;
+    return SSDNERF_OK;
+}
+
+extern "C" int ssdnerf_perm_indices(int64_t* out, uint32_t S, uint64_t P, uint64_t start, uint32_t R, uint64_t seed, uint32_t draw, void* stream) {
+    SSD_REQUIRE(out != nullptr, "perm_indices: null pointer");
+    uint32_t bps = 0;
+    const int status = rp_check("perm_indices", S, P, start, R, &bps);
+    if (status != SSDNERF_OK) return status;
+    SSD_REQUIRE(((uintptr_t)out & 7u) == 0, "perm_indices: out is not 8-byte aligned");
+    hipLaunchKernelGGL(k_perm_indices, dim3(S * bps), dim3(RS_THREADS), 0, (hipStream_t)stream, out, (uint32_t)P, (uint32_t)start, R, bps, sskp_half_bits(P),
+                       seed, draw);
+    SSD_CHECK_LAUNCH("perm_indices");
+    return SSDNERF_OK;
+}
+
+extern "C" int ssdnerf_sample_rays_perm_u8(const uint8_t* store, uint64_t num_images, uint32_t h, uint32_t w, const int32_t* view_image, const float* c2w,
+                                           const float* intr, uint32_t S, uint32_t V, uint64_t seed, uint32_t draw, uint64_t start, uint32_t R,
+                                           float* rays_o, float* rays_d, float* target, void* stream) {
+    SSD_REQUIRE(store != nullptr && view_image != nullptr && c2w != nullptr && intr != nullptr, "sample_rays_perm_u8: null input pointer");
+    SSD_REQUIRE(rays_o != nullptr && rays_d != nullptr && target != nullptr, "sample_rays_perm_u8: null output pointer");
+    SSD_REQUIRE(V > 0 && h > 0 && w > 0, "sample_rays_perm_u8: no pixels (V = %u, h = %u, w = %u)", V, h, w);
+    SSD_REQUIRE(num_images > 0, "sample_rays_perm_u8: num_images == 0 (an empty store)");
+    SSD_REQUIRE(num_images <= 0x7fffffffull, "sample_rays_perm_u8: %llu images, the int32 table reaches 2^31 - 1", (unsigned long long)num_images);
+    const uint64_t hw = (uint64_t)h * w;
+    SSD_REQUIRE(hw < ((uint64_t)1 << 32) && hw * V < ((uint64_t)1 << 32), "sample_rays_perm_u8: V * h * w is 2^32 pixels per scene or more");
+    uint32_t bps = 0;
+    const int status = rp_check("sample_rays_perm_u8", S, hw * V, start, R, &bps);
+    if (status != SSDNERF_OK) return status;
+    SSD_REQUIRE((((uintptr_t)rays_o | (uintptr_t)rays_d | (uintptr_t)target | (uintptr_t)view_image | (uintptr_t)c2w | (uintptr_t)intr) & 3u) == 0,
+                "sample_rays_perm_u8: an output or a table is not 4-byte aligned");
+    hipLaunchKernelGGL(k_sample_rays_perm_u8, dim3(S * bps), dim3(RS_THREADS), 0, (hipStream_t)stream, store, (uint32_t)hw, w, view_image, c2w, intr, V,
+                       (uint32_t)(hw * V), (uint32_t)start, R, bps, sskp_half_bits(hw * V), seed, draw, rays_o, rays_d, target);
+    SSD_CHECK_LAUNCH("sample_rays_perm_u8");
     return SSDNERF_OK;
 }

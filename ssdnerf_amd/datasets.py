@@ -430,10 +430,12 @@ class StoredViews:
     ``sample(inds)``  (rays_o, rays_d, target), each (S, R, 3): pixels ``inds`` (S, R) int64 on the device -- or every pixel, ``None`` -- with
                       their rays, from ONE launch of ``ssdnerf_sample_rays_u8`` (csrc/scene_store.hip), bit for bit what indexing the dense
                       arrays gives.  An index outside [0, V*h*w) gives a NaN ray.
+    ``sample_permuted(seed, draw, start, count)``  the same three arrays for the pixels at positions start .. start + count - 1 of a keyed permutation
+                      that the kernel evaluates itself (``ssdnerf_sample_rays_perm_u8``): no index tensor exists.
     ``dense()``       (images, rays_o, rays_d), each (S, V, h, w, 3): the arrays themselves, by ``SceneStore.gather`` and ``nerf.get_cam_rays``,
                       built on the first call and kept -- for consumers that need whole images.
 
-    ``sample_launches`` counts the calls of ``sample``; ``dense_calls`` the times the dense arrays were built (0 or 1)."""
+    ``sample_launches`` counts the calls of ``sample`` and ``sample_permuted``; ``dense_calls`` the times the dense arrays were built (0 or 1)."""
 
     dtype = torch.float32
 
@@ -480,6 +482,25 @@ class StoredViews:
             C.check(C.lib().ssdnerf_sample_rays_u8(C.ptr(self.store.pixels), self.store.num_images, h, w, C.ptr(self.view_image_dev), C.ptr(self.poses),
                                                    C.ptr(self.intrinsics), S, V, C.ptr(inds), R, C.ptr(rays_o), C.ptr(rays_d), C.ptr(target),
                                                    C.stream()), "sample_rays_u8")
+        self.sample_launches += 1
+        return rays_o, rays_d, target
+
+    def sample_permuted(self, seed: int, draw: int, start: int, count: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """``sample`` without an index tensor: ray r of scene s is pixel pi(seed, s, draw, V*h*w)(start + r) of the keyed permutation of
+        csrc/keyed_perm.h, r < ``count``, evaluated inside ONE launch of ``ssdnerf_sample_rays_perm_u8`` -- bit for bit what ``sample`` gives on the
+        indices ``ssdnerf_perm_indices`` writes for the same arguments.  ``start + count`` may not pass V*h*w."""
+        from . import _cabi as C
+        S, V, h, w, _ = self.shape
+        seed, draw, start, count = int(seed), int(draw), int(start), int(count)
+        if not (0 <= seed < 1 << 64 and 0 <= draw < 1 << 32):
+            raise ValueError(f"StoredViews.sample_permuted: seed must fit 64 bits and draw 32, got {seed} and {draw}")
+        if not (start >= 0 and count > 0 and start + count <= V * h * w):
+            raise ValueError(f"StoredViews.sample_permuted: positions [{start}, {start} + {count}) leave the {V * h * w} pixels of a scene")
+        with torch.cuda.device(self.device):
+            rays_o, rays_d, target = (torch.empty((S, count, 3), dtype=torch.float32, device=self.device) for _ in range(3))
+            C.check(C.lib().ssdnerf_sample_rays_perm_u8(C.ptr(self.store.pixels), self.store.num_images, h, w, C.ptr(self.view_image_dev), C.ptr(self.poses),
+                                                        C.ptr(self.intrinsics), S, V, seed, draw, start, count, C.ptr(rays_o), C.ptr(rays_d),
+                                                        C.ptr(target), C.stream()), "sample_rays_perm_u8")
         self.sample_launches += 1
         return rays_o, rays_d, target
 

@@ -80,19 +80,42 @@ class Conditioning:
         return self._arrays[0].shape[1:4].numel()
 
 
+INDEX_SOURCES = ("host", "device")
+
+
+def check_index_source(value) -> str:
+    """``cfg['ray_index_source']``: 'host' (torch.randperm, the default) or 'device' (the keyed permutation of csrc/keyed_perm.h)"""
+    if value not in INDEX_SOURCES:
+        raise ValueError(f"ray_index_source must be one of {INDEX_SOURCES}, got {value!r}")
+    return value
+
+
 class RayBatcher:
     """``batch(k)`` -> (rays_o, rays_d, target), each (S, R, 3).  With more pixels than ``rays_per_step`` the pixels of every scene are
     permuted once and step k takes chunk k mod n_chunks (``fixed=True``: base_nerf.py:263-274, used by inversion and guidance), or a fresh
     random subset is drawn per call (``fixed=False``: base_nerf.py:231-261 without indices, used by ``loss_decoder``).  On a store-backed
-    ``Conditioning`` the indices are drawn by the same calls in the same order and the gather is ``StoredViews.sample``: one launch per batch."""
+    ``Conditioning`` the indices are drawn by the same calls in the same order and the gather is ``StoredViews.sample``: one launch per batch.
 
-    def __init__(self, cond: Conditioning, rays_per_step: int, fixed: bool = True):
+    ``index_source='device'`` (opt-in) draws no index on the host: pixel numbers are positions of the keyed permutation
+    pi(seed, scene, draw, P) of csrc/keyed_perm.h.  ``fixed=True``: chunk k is positions [kR, min((k+1)R, P)) of draw 0, cycled after ceil(P/R)
+    chunks as the host chunks are; ``fixed=False``: take number n is positions [0, R) of draw n.  A store-backed conditioning evaluates pi inside
+    the sampling launch (``StoredViews.sample_permuted``), a dense one indexes with the output of ``ssdnerf_perm_indices``: the same pixels.
+    ``seed=None`` takes one 64-bit draw from torch's CPU generator here, so ``torch.manual_seed`` reproduces a run.  Not torch.randperm's stream."""
+
+    def __init__(self, cond: Conditioning, rays_per_step: int, fixed: bool = True, index_source: str = "host", seed: Optional[int] = None):
+        self.index_source = check_index_source(index_source)
         self.S, self.P, self.R = cond.num_scenes, cond.pixels_per_scene, rays_per_step
         self.stored, self.device = cond.stored, cond.device
+        if index_source == "device" and self.device.type != "cuda":
+            raise ValueError(f"RayBatcher: index_source='device' draws on the GPU, the conditioning is on {self.device} (there is no CPU path)")
         self.flat = None
         if self.stored is None:
             self.flat = (cond.rays_o.reshape(self.S, self.P, 3), cond.rays_d.reshape(self.S, self.P, 3), cond.images.reshape(self.S, self.P, 3))
         self.chunks: Optional[Sequence[torch.Tensor]] = None
+        self.fixed, self.n_chunks, self.takes = fixed, -(-self.P // self.R), 0
+        if index_source == "device":
+            self.seed = (int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64)) if seed is None else int(seed)) & (2 ** 64 - 1)
+            return
         if fixed and self.P > self.R:
             perms = torch.stack([torch.randperm(self.P, device=self.device) for _ in range(self.S)], dim=0)
             if self.stored is None:
@@ -103,12 +126,37 @@ class RayBatcher:
                 if whole * self.R < self.P:
                     self.chunks += (perms[:, whole * self.R:].contiguous(),)
 
+    def _span(self, k: int):
+        """(draw, start, count) of batch k in device mode: a chunk of draw 0, or the head of the next unused draw"""
+        if self.fixed:
+            start = (k % self.n_chunks) * self.R
+            return 0, start, min(self.R, self.P - start)
+        self.takes += 1
+        return self.takes - 1, 0, self.R
+
+    def device_indices(self, draw: int, start: int, count: int) -> torch.Tensor:
+        """(S, count) int64: pi(seed, s, draw, P)(start + r), one launch of ``ssdnerf_perm_indices``"""
+        from . import _cabi as C
+        with torch.cuda.device(self.device):
+            inds = torch.empty((self.S, count), dtype=torch.int64, device=self.device)
+            C.check(C.lib().ssdnerf_perm_indices(C.ptr(inds), self.S, self.P, start, count, self.seed, draw, C.stream()), "perm_indices")
+        return inds
+
+    def _permuted(self, draw: int, start: int, count: int):
+        if self.stored is not None:                  # pi is evaluated inside the sampling launch: no index tensor
+            return self.stored.sample_permuted(self.seed, draw, start, count)
+        return self.take(self.device_indices(draw, start, count))
+
     def indices(self, k: int) -> Optional[torch.Tensor]:
+        if self.index_source == "device":
+            return self.device_indices(*self._span(k)) if self.fixed and self.P > self.R else None
         return None if self.chunks is None else self.chunks[k % len(self.chunks)]
 
     def take(self, inds: Optional[torch.Tensor]):
         if self.P <= self.R:
             return self.flat if self.stored is None else self.stored.sample(None)
+        if inds is None and self.index_source == "device":
+            return self._permuted(*self._span(0))
         if inds is None:
             inds = torch.stack([torch.randperm(self.P, device=self.device)[:self.R] for _ in range(self.S)], dim=0)
         if self.stored is not None:
@@ -117,6 +165,8 @@ class RayBatcher:
         return tuple(t[rows, inds] for t in self.flat)
 
     def batch(self, k: int):
+        if self.index_source == "device" and self.fixed and self.P > self.R:
+            return self._permuted(*self._span(k))
         return self.take(self.indices(k))
 
 
@@ -138,7 +188,7 @@ class CodeFitter:
         self.code_, self.grid, self.bits = code_, density_grid, density_bitfield
         self.optimizers = list(optimizers) if isinstance(optimizers, (list, tuple)) else [optimizers]
         self.schedulers = [] if schedulers is None else (list(schedulers) if isinstance(schedulers, (list, tuple)) else [schedulers])
-        self.batcher = RayBatcher(cond, cfg.get("n_inverse_rays", 4096), fixed=True)
+        self.batcher = RayBatcher(cond, cfg.get("n_inverse_rays", 4096), fixed=True, index_source=cfg.get("ray_index_source", "host"))
         self.march_noises, self.density_jitters = _as_iter(march_noises), _as_iter(density_jitters)
         self.k = 0
         self.last = None            # (code, loss, loss_dict, rendered rgb, target rgb) of the latest iteration
@@ -200,7 +250,7 @@ class GuidanceObjective:
         dev, S, H3 = cond.device, cond.num_scenes, model.grid_size ** 3
         self.grid = torch.zeros((S, H3), device=dev)                                   # fp32 here, as in the reference (diffusion_nerf.py:278)
         self.bits = torch.zeros((S, H3 // 8), dtype=torch.uint8, device=dev)
-        self.batcher = RayBatcher(cond, cfg.get("n_inverse_rays", 4096), fixed=True)
+        self.batcher = RayBatcher(cond, cfg.get("n_inverse_rays", 4096), fixed=True, index_source=cfg.get("ray_index_source", "host"))
         self.march_noises, self.density_jitters = march_noises, density_jitters
         self.calls = 0
 

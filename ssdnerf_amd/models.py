@@ -29,7 +29,7 @@ from .codes import attr_path_get, attr_path_set, frozen
 from .codes import IdentityCode, MSELoss, NormalizedTanhCode, RegLoss, TanhCode, TVLoss  # noqa: F401  (registered here for config builds)
 from .density import get_density as _get_density, update_density_grid
 from .datasets import StoredViews
-from .fitting import CodeFitter, Conditioning, GuidanceObjective, RayBatcher
+from .fitting import CodeFitter, Conditioning, GuidanceObjective, RayBatcher, check_index_source
 from .metrics import image_metrics
 from .optim import HIPAdam, step_all
 from .registry import MODELS, build_module, get_module_device
@@ -59,6 +59,8 @@ class BaseNeRF(nn.Module):
         self.pixel_loss = build_module(pixel_loss)
         self.reg_loss = None if reg_loss is None else build_module(reg_loss)
         self.train_cfg, self.test_cfg = dict(train_cfg or {}), dict(test_cfg or {})
+        for cfg in (self.train_cfg, self.test_cfg):     # 'host' (torch.randperm, the default) | 'device' (csrc/keyed_perm.h)
+            check_index_source(cfg.get("ray_index_source", "host"))
         self.update_extra_interval = update_extra_interval
         # LPIPS of the test views: computed when this is set AND a net is present (set_lpips, or test_cfg['lpips_weights'] on first use).  The net
         # lives in a plain list: not a submodule, so never part of state_dict() (the reference holds its lpips net the same way)
@@ -241,7 +243,12 @@ class BaseNeRF(nn.Module):
         was_training = decoder.training
         decoder.train(True)
         try:
-            rays_o, rays_d, target = self.ray_sample(cond_rays_o, cond_rays_d, cond_imgs, n_samples=cfg.get("n_decoder_rays", 4096))
+            n_rays = cfg.get("n_decoder_rays", 4096)
+            if check_index_source(cfg.get("ray_index_source", "host")) == "host":
+                rays_o, rays_d, target = self.ray_sample(cond_rays_o, cond_rays_d, cond_imgs, n_samples=n_rays)
+            else:   # draw 0 of a batcher seeded from torch's CPU generator, per call: the pixel numbers are made on the device (fitting.RayBatcher)
+                rays_o, rays_d, target = RayBatcher(Conditioning(cond_imgs, cond_rays_o, cond_rays_d, None), n_rays, fixed=False,
+                                                    index_source="device").take(None)
             rgb, total, parts = self.loss(decoder, code, density_bitfield, target, rays_o, rays_d, dt_gamma, return_decoder_loss=True,
                                           scale_num_ray=(cond_imgs if cond_rays_o is None else cond_rays_o).shape[1:4].numel(), cfg=cfg, **kwargs)
         finally:
