@@ -165,6 +165,11 @@ int ssdnerf_march_rays_train_batch_write(const float* rays_o, const float* rays_
  * 64 samples (bf16-pair operands, fp32 accumulation: the arithmetic class of the UNet's fp32-class kernels) instead of fp32 fused multiply-adds on the vector ALUs. */
 #define SSDNERF_DECODE_BWD_FEAT_MFMA 0x100
 size_t ssdnerf_point_decode_backward_workspace(uint32_t S, uint32_t total, uint32_t Hp, uint32_t Wp);
+/* Where one backward keeps its intermediates inside that workspace (for tests that read them back after the call): out[0..4] = byte offsets of
+ * counters [S][32] uint32 (samples with a gradient per scene, at [s][0]), keys [3][total] uint32 (y0 << 16 | x0), pos [3][total] float2 (clipped texel
+ * coordinates), gfeat [3][total][6] float, partial [K][S][3][Hp][Wp][6] float; out[5] = the split count K.  The three per-sample arrays are indexed by
+ * compacted slot: offsets[s] + rank among the scene's samples with a gradient. */
+void ssdnerf_point_decode_backward_layout(uint32_t S, uint32_t total, uint32_t Hp, uint32_t Wp, uint64_t out[6]);
 int ssdnerf_point_decode_backward(const void* planes, int planes_dtype, uint32_t S, uint32_t Hp, uint32_t Wp, const float* mlp_params,
                                   const float* xyzs, const float* dirs, const uint32_t* offsets, uint32_t total,
                                   float sigmoid_saturation, const float* grad_sigmas, const float* grad_rgbs, float* grad_code,

@@ -162,6 +162,17 @@ extern "C" size_t ssdnerf_point_decode_backward_workspace(uint32_t S, uint32_t t
     return db_workspace(nullptr, S, total, Hp, Wp).bytes;
 }
 
+// where the intermediates of one backward sit inside its workspace: byte offsets of counters, keys, pos, gfeat, partial, then the split count K
+extern "C" void ssdnerf_point_decode_backward_layout(uint32_t S, uint32_t total, uint32_t Hp, uint32_t Wp, uint64_t out[6]) {
+    const DecodeBwdWs w = db_workspace(nullptr, S, total, Hp, Wp);
+    out[0] = (uint64_t)(uintptr_t)w.counters;
+    out[1] = (uint64_t)(uintptr_t)w.keys;
+    out[2] = (uint64_t)(uintptr_t)w.pos;
+    out[3] = (uint64_t)(uintptr_t)w.gfeat;
+    out[4] = (uint64_t)(uintptr_t)w.partial;
+    out[5] = w.K;
+}
+
 SSD_DEV uint32_t db_scene_of(const uint32_t* __restrict__ offsets, uint32_t S, uint32_t i) {
     uint32_t scene = 0;
     while (scene + 1 < S && i >= offsets[scene + 1]) ++scene;

@@ -204,8 +204,10 @@ def sigmoid_terms(h, Bh):
 
 
 # ------------------------------------------------------------------------------------------------ per sample
-def decode_ref(P, code, xyz, dirs, sat, mfma, density_only=False):
-    """(sigma [N], B_sigma [N], rgb [N, 3], B_rgb [N, 3]) of ``ssd_mlp`` on ``ssd_gather18``'s features, float64:
+def decode_terms(P, code, xyz, dirs, sat, mfma, density_only=False):
+    """``ssd_mlp`` on ``ssd_gather18``'s features in float64, every quantity with its carried bound, as a namespace: the outputs sigma [N], B_sigma, rgb [N, 3], B_rgb
+    (what ``decode_ref`` returns) and the features f, pre-activations h, h + d (``hc``), sa, z with B_f, B_h, B_hc, B_sa, B_z and the layer magnitudes S1, Sd, which
+    the decode gradient's reference (tests/_decode_grad_ref.py) starts from.  ``mfma`` may also be a dict of another kernel's layer allowances (see below).
         h = W1 f + b1;  sigma = exp(w_sigma . silu(h) + b_sigma);  rgb = sigmoid(Wc silu(h + Wd SH4(d) + bd) + bc) (1 + 2 sat) - sat.
     Bounds, S_* = sum of the magnitudes of a layer's terms and its bias, B_* carried:
       h:       |W1| B_f + K_BASE u S_1                                        MFMA: (K_BASE_MFMA + SPLIT + PRESCALE) u S_1
@@ -218,21 +220,25 @@ def decode_ref(P, code, xyz, dirs, sat, mfma, density_only=False):
     f, Bf = gather18(code, xyz)
     aW1 = np.abs(p.W1)
     h, S1 = f @ p.W1.T + p.b1, np.abs(f) @ aW1.T + np.abs(p.b1)
-    Bh = Bf @ aW1.T + ((K_BASE_MFMA + SPLIT + PRESCALE) if mfma else K_BASE) * U32 * S1
-    k_out = K_OUT_MFMA if mfma else K_OUT
+    own = mfma if isinstance(mfma, dict) else None      # another kernel's layer allowances {"base", "dir", "out"}, in the VALU class's shape (tests/_decode_grad_ref.py)
+    Bh = Bf @ aW1.T + (own["base"] if own else (K_BASE_MFMA + SPLIT + PRESCALE) if mfma else K_BASE) * U32 * S1
+    k_out = own["out"] if own else K_OUT_MFMA if mfma else K_OUT
     s, Bs = silu_terms(h, Bh)
     sa = s @ p.ws + p.bs
     Bsa = Bs @ np.abs(p.ws) + k_out * U32 * (np.abs(s) @ np.abs(p.ws) + abs(p.bs))
     assert float(Bsa.max(initial=0.0)) < GUARD, ("first order does not hold: density pre-activation bound", float(Bsa.max()))
     sigma = np.exp(sa)
     Bsigma = sigma * (Bsa * (1.0 + Bsa) + (np.abs(sa) + C_EXP) * U32)
+    out = SimpleNamespace(p=p, f=f, B_f=Bf, h=h, B_h=Bh, S1=S1, sa=sa, B_sa=Bsa, sigma=sigma, B_sigma=Bsigma, rgb=None, B_rgb=None)
     if density_only:
-        return sigma, Bsigma, None, None
+        return out
     sh, Bsh = sh4(dirs)
     aWd = np.abs(p.Wd)
     d, Sd = sh @ p.Wd.T + p.bd, np.abs(sh) @ aWd.T + np.abs(p.bd)
     hc = h + d
-    if mfma:
+    if own:
+        Bhc = Bh + Bsh @ aWd.T + own["dir"] * U32 * Sd + U32 * np.abs(hc)
+    elif mfma:
         Bhc = Bh + Bsh @ aWd.T + (SPLIT + PRESCALE) * U32 * Sd + K_DIR_MFMA * U32 * (S1 + Sd)
     else:
         Bhc = Bh + Bsh @ aWd.T + K_DIR * U32 * Sd + U32 * np.abs(hc)
@@ -243,7 +249,14 @@ def decode_ref(P, code, xyz, dirs, sat, mfma, density_only=False):
     sg, Bsg = sigmoid_terms(pc, Bpc)
     k = 1.0 + 2.0 * sat
     rgb = sg * k - sat
-    return sigma, Bsigma, rgb, k * Bsg + U32 * (k * sg + np.abs(rgb))
+    out.__dict__.update(sh=sh, B_sh=Bsh, Sd=Sd, hc=hc, B_hc=Bhc, z=pc, B_z=Bpc, rgb=rgb, B_rgb=k * Bsg + U32 * (k * sg + np.abs(rgb)))
+    return out
+
+
+def decode_ref(P, code, xyz, dirs, sat, mfma, density_only=False):
+    """(sigma [N], B_sigma [N], rgb [N, 3], B_rgb [N, 3]) of ``decode_terms``"""
+    t = decode_terms(P, code, xyz, dirs, sat, mfma, density_only)
+    return t.sigma, t.B_sigma, t.rgb, t.B_rgb
 
 
 def folded_column_ref(P):
