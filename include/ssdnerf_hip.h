@@ -318,6 +318,34 @@ int ssdnerf_sde_step_v(const float* x_t, const float* v, const float* x0_prev, u
                        void* stream);
 uint32_t ssdnerf_sde_block_cap(void);
 
+/* The diffusion prior loss around the UNet on device noise (csrc/prior_loss.hip; diffusion.GaussianDiffusion.forward_train with
+ * noise_source='device').  THE PRIOR CONTRACT, common to the three entries:
+ *   the latent is (B, n_per) flattened, n_per % 4 == 0; element i of the flattened latent takes its normal z_i from quad i / 4 of the generator
+ *   above: bit for bit what ssdnerf_philox_normal_fill(out, B * n_per, seed, draw) stores at i; z is never written to memory.
+ *   a[s], b[s], k[s]: device arrays of B floats (sqrt(abar) and sqrt(1 - abar) at each sample's timestep; k below).
+ *   Every product and sum rounds on its own, in the order written.  No floating-point atomics: equal inputs give equal bits on every run.
+ *   pred_dtype: 0 fp32, 2 bf16 (a bf16 value widens exactly).  x0 and the fp32 arrays are 16-byte aligned, bf16 arrays 8-byte aligned.
+ *   A null required pointer, n_per % 4 != 0, another dtype code, B > 2^20 and a misaligned array fail with SSDNERF_E_INVALID before any HIP call;
+ *   B == 0 or n_per == 0 is a no-op.
+ * ssdnerf_prior_q_sample:   x_t = x0 * a_s + z * b_s.  x_t_out == x0 is refused.
+ * ssdnerf_prior_loss_v:     diff = pred - (a_s * z - b_s * x0);  msd_out[s] = mean_i diff^2,  x0sq_out[s] = mean_i x0^2 (fp32, B each).
+ *   The sums have a fixed order: a lane adds the squares of its elements in index order, one float4 per trip of the grid-stride loop; an xor butterfly over
+ *   the wave's 64 lanes; the block's four waves in wave order; one partial per block into partials [2][B][blocks_per_sample] (caller-owned,
+ *   ssdnerf_prior_loss_partials(B, n_per) floats, no initialisation needed); then one wave per sample adds its partials l, l + 64, ... per lane, a
+ *   butterfly, and ONE division by n_per.  ssdnerf_prior_blocks_per_sample(n_per) = min(ceil(n_per / 1024), ssdnerf_prior_block_cap()).
+ * ssdnerf_prior_loss_v_backward:   g = k_s * diff (diff recomputed as above; k_s = the gradient arriving at msd[s], times 2 / n_per);
+ *   grad_pred_out = g in pred's dtype (bf16: round to nearest even);  grad_x0_out = g * b_s in fp32 -- the path through the target only -- or NULL:
+ *   then it is not written. */
+int ssdnerf_prior_q_sample(const float* x0, const float* a, const float* b, uint32_t B, uint64_t n_per, uint64_t seed, uint32_t draw,
+                           float* x_t_out, void* stream);
+int ssdnerf_prior_loss_v(const void* pred, int pred_dtype, const float* x0, const float* a, const float* b, uint32_t B, uint64_t n_per,
+                         uint64_t seed, uint32_t draw, float* partials, float* msd_out, float* x0sq_out, void* stream);
+int ssdnerf_prior_loss_v_backward(const void* pred, int pred_dtype, const float* x0, const float* a, const float* b, const float* k, uint32_t B,
+                                  uint64_t n_per, uint64_t seed, uint32_t draw, void* grad_pred_out, float* grad_x0_out, void* stream);
+uint32_t ssdnerf_prior_block_cap(void);
+uint32_t ssdnerf_prior_blocks_per_sample(uint64_t n_per);
+uint64_t ssdnerf_prior_loss_partials(uint32_t B, uint64_t n_per);
+
 /* Camera rays of n_views pinhole views (get_cam_rays, lib/core/utils/nerf_utils.py:17-61): c2w [n_views][4][4] row-major,
  * intrinsics [n_views][4] = {fx, fy, cx, cy}; rays_o, rays_d [n_views][h][w][3]: pixel-centre (x + 0.5) directions rotated by
  * c2w[:3,:3] and L2-normalised, origins c2w[:3,3] broadcast. */

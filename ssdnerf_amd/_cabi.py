@@ -18,6 +18,7 @@ _lib: Optional[ctypes.CDLL] = None
 
 ABI_VERSION = 3
 F32, F16 = 0, 1
+BF16 = 2        # (the prior-loss entries and the scene cache; ``dtype_code`` serves the fp32 / fp16 operators)
 
 EXPORTS = [
     "ssdnerf_last_error", "ssdnerf_abi_version", "ssdnerf_near_far_from_aabb", "ssdnerf_sph_from_ray", "ssdnerf_morton3D",
@@ -41,6 +42,8 @@ EXPORTS = [
     "ssdnerf_dpmpp_step_v", "ssdnerf_dpmpp_block_cap",
     "ssdnerf_png_filter_rows", "ssdnerf_code_plane_rgb",
     "ssdnerf_philox_normal_fill", "ssdnerf_sde_step_v", "ssdnerf_sde_block_cap",
+    "ssdnerf_prior_q_sample", "ssdnerf_prior_loss_v", "ssdnerf_prior_loss_v_backward", "ssdnerf_prior_block_cap", "ssdnerf_prior_blocks_per_sample",
+    "ssdnerf_prior_loss_partials",
 ]
 
 
@@ -142,7 +145,17 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_philox_normal_fill.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_void_p]
         l.ssdnerf_sde_step_v.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint64, ctypes.c_int] + [ctypes.c_float] * 8 + \
                                         [ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 3
-        l.ssdnerf_png_filter_rows.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 2
+        l.ssdnerf_prior_block_cap.restype = l.ssdnerf_prior_blocks_per_sample.restype = ctypes.c_uint32
+        l.ssdnerf_prior_block_cap.argtypes = []
+        l.ssdnerf_prior_blocks_per_sample.argtypes = [ctypes.c_uint64]
+        l.ssdnerf_prior_loss_partials.restype = ctypes.c_uint64
+        l.ssdnerf_prior_loss_partials.argtypes = [ctypes.c_uint32, ctypes.c_uint64]
+        l.ssdnerf_prior_q_sample.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 2
+        l.ssdnerf_prior_loss_v.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 3 + \
+                                          [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 4
+        l.ssdnerf_prior_loss_v_backward.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_void_p] * 4 + \
+                                                   [ctypes.c_uint32, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32] + [ctypes.c_void_p] * 3
+        l.ssdnerf_png_filter_rows.argtypes =[ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 2
         l.ssdnerf_code_plane_rgb.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] * 4 + [ctypes.c_float] * 2 + [ctypes.c_int] + [ctypes.c_void_p] * 2
         if l.ssdnerf_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libssdnerf_hip.so ABI {l.ssdnerf_abi_version()} != expected {ABI_VERSION}: rebuild")

@@ -16,6 +16,9 @@ methods are the reference's; the implementation is organised for the MI355X inst
   step -- DDIM with eta > 0, Langevin corrections, the ancestral sampler, ``sample_method='dpmpp_2m_sde'`` (SDE-DPM-Solver++(2M); not in the
   reference, opt-in) -- stays in the session too: ``ssdnerf_sde_step_v`` makes its normals in registers from a counter-based generator
   (csrc/philox.h) keyed by ``test_cfg['noise_seed']``; the tensor-expression branch takes the same normals from ``ssdnerf_philox_normal_fill``.
+* ``cfg['noise_source']='device'`` in ``forward_train`` (opt-in, ``train_cfg`` / ``test_cfg``): the prior loss takes its noise from the
+  same generator under draws numbered 0x80000000 | k, and the arithmetic around the UNet -- q_sample, the V target, the per-sample mean of squares, their
+  gradients -- is three launches of csrc/prior_loss.hip that make the normals in registers; what follows the mean stays in ``DDPMMSELossMod``.
 * The guided step (rendering guidance, SSDNeRF's ``grad_guide_fn``) needs autograd through the UNet and the renderer; it keeps tensors in
   the graph exactly where the reference does, with the coefficients coming from the plan as Python floats.
 """
@@ -104,6 +107,69 @@ def _host_noise(like: torch.Tensor) -> torch.Tensor:
     if like.is_cuda:
         return _PinnedRing.upload(like.shape, like.device)
     return torch.randn(like.shape, dtype=torch.float32).to(like.device)
+
+
+# ============================================================================================== the prior loss on device noise (csrc/prior_loss.hip)
+_LOSS_DRAW_BASE = 1 << 31           # loss draws are numbered 0x80000000 | k: never one of the sampling draws 0, 1, 2, ... of ``_run_plan`` under the same seed
+_PRIOR_DTYPES = {torch.float32: C.F32, torch.bfloat16: C.BF16}
+_PRIOR_SLAB: Dict = {}              # (B, n_per) -> ssdnerf_prior_loss_partials(B, n_per), asked once per shape
+
+
+def _prior_args(x0, a, b, seed, draw):
+    B = x0.size(0)
+    n_per = x0.numel() // B if B else 0
+    return [C.ptr(a), C.ptr(b), C.u32(B), C.ctypes.c_uint64(n_per), C.ctypes.c_uint64(int(seed) & _U64), C.u32(draw)]
+
+
+class _PriorQSample(torch.autograd.Function):
+    """x_t = a_s x0 + b_s z, z the normals of (seed, draw) made in registers (``ssdnerf_prior_q_sample``); d x_t / d x0 = a_s.
+    ``x0`` (B, ...) fp32 contiguous on the GPU, ``a`` / ``b`` (B,) fp32 contiguous."""
+
+    @staticmethod
+    def forward(ctx, x0, a, b, seed, draw):
+        x_t = torch.empty_like(x0)
+        C.check(C.lib().ssdnerf_prior_q_sample(C.ptr(x0), *_prior_args(x0, a, b, seed, draw), C.ptr(x_t), C.stream()), "prior_q_sample")
+        ctx.save_for_backward(a)
+        return x_t
+
+    @staticmethod
+    def backward(ctx, grad):
+        (a,) = ctx.saved_tensors
+        return grad * a.reshape(-1, *([1] * (grad.dim() - 1))), None, None, None, None
+
+
+class _PriorLossV(torch.autograd.Function):
+    """(msd, x0sq) per sample of the V-parameterised loss: msd = mean_i (pred - (a_s z - b_s x0))^2, x0sq = mean_i x0^2 (``ssdnerf_prior_loss_v``;
+    x0sq carries no gradient: it feeds ``norm_factor`` only).  Backward: ``ssdnerf_prior_loss_v_backward`` recomputes the difference from the same
+    (seed, draw); the gradient on x0 is the path through the target alone, the path through x_t belongs to ``_PriorQSample``."""
+
+    @staticmethod
+    def forward(ctx, pred, x0, a, b, seed, draw):
+        B = x0.size(0)
+        lib = C.lib()
+        n_per = x0.numel() // B if B else 0
+        if (B, n_per) not in _PRIOR_SLAB:
+            _PRIOR_SLAB[B, n_per] = int(lib.ssdnerf_prior_loss_partials(B, n_per))
+        buf = torch.empty(2 * B + _PRIOR_SLAB[B, n_per], dtype=torch.float32, device=x0.device)      # msd | x0sq | the slab of block partials: one allocation
+        msd, x0sq, partials = buf[:B], buf[B:2 * B], buf[2 * B:]
+        C.check(lib.ssdnerf_prior_loss_v(C.ptr(pred), _PRIOR_DTYPES[pred.dtype], C.ptr(x0), *_prior_args(x0, a, b, seed, draw), C.ptr(partials),
+                                         C.ptr(msd), C.ptr(x0sq), C.stream()), "prior_loss_v")
+        ctx.save_for_backward(pred, x0, a, b)
+        ctx.seed, ctx.draw = seed, draw
+        ctx.mark_non_differentiable(x0sq)
+        return msd, x0sq
+
+    @staticmethod
+    def backward(ctx, grad_msd, _grad_x0sq):
+        pred, x0, a, b = ctx.saved_tensors
+        n_per = x0.numel() // x0.size(0) if x0.size(0) else 1
+        k = (grad_msd.float() * (2.0 / n_per)).contiguous()
+        grad_pred = torch.empty_like(pred)
+        grad_x0 = torch.empty_like(x0) if ctx.needs_input_grad[1] else None
+        C.check(C.lib().ssdnerf_prior_loss_v_backward(C.ptr(pred), _PRIOR_DTYPES[pred.dtype], C.ptr(x0), C.ptr(a), C.ptr(b), C.ptr(k),
+                                                      *_prior_args(x0, a, b, ctx.seed, ctx.draw)[2:], C.ptr(grad_pred), C.ptr(grad_x0), C.stream()),
+                "prior_loss_v_backward")
+        return grad_pred, grad_x0, None, None, None, None
 
 
 # ============================================================================================== schedule
@@ -348,9 +414,16 @@ class DDPMMSELossMod(nn.Module):
 
     def forward(self, output_dict):
         assert isinstance(output_dict, dict) and "timesteps" in output_dict, "DDPM losses take the dict of network outputs with 'timesteps'"
-        t = output_dict["timesteps"]
         diff = output_dict[self.data_info["pred"]] - output_dict[self.data_info["target"]]
-        per_sample = diff.square().flatten(1).mean(dim=1) * 0.5
+        return self._from_msd(diff.square().flatten(1).mean(dim=1), output_dict["timesteps"], lambda: output_dict["x_0"].detach().square().mean())
+
+    def forward_msd(self, msd, timesteps, x0sq):
+        """``forward`` from the per-sample reductions alone: ``msd`` (B,) = mean_i (pred - target)^2 and ``x0sq`` (B,) = mean_i x_0^2 per sample, as the
+        fused kernels of csrc/prior_loss.hip return them (``norm_factor`` is fed ``x0sq.mean()``).  Everything behind the mean is ``forward``'s own code."""
+        return self._from_msd(msd, timesteps, lambda: x0sq.detach().mean())
+
+    def _from_msd(self, msd, t, x0_square_mean):
+        per_sample = msd * 0.5
         if self.timestep_weight is not None:
             if self.timestep_weight.device != t.device:
                 self.timestep_weight = self.timestep_weight.to(t.device)                                 # moved once, not per call
@@ -360,7 +433,7 @@ class DDPMMSELossMod(nn.Module):
         if self.scale_norm:
             if self.training and not self.freeze_norm:
                 from .parallel import reduce_mean
-                self.norm_factor.mul_(1 - self.momentum).add_(self.momentum * reduce_mean(output_dict["x_0"].detach().square().mean()))
+                self.norm_factor.mul_(1 - self.momentum).add_(self.momentum * reduce_mean(x0_square_mean()))
             loss = loss / self.norm_factor
         return loss
 
@@ -652,12 +725,76 @@ class GaussianDiffusion(nn.Module):
             fields["v_t"] = mean * noise - std * x_0
         return self.ddpm_loss(fields)
 
-    def forward_train(self, x_0, concat_cond=None, grad_guide_fn=None, cfg=dict(), x_t_detach=False, timesteps=None, noise=None, **kwargs):
+    def _loss_draw(self, cfg, noise_seed, noise_draw):
+        """(seed, draw) of one device-mode loss call.  Seed: ``cfg['noise_seed']`` plus the ``torch.distributed`` rank (mod 2^64) when set; otherwise ONE
+        64-bit draw from torch's CPU generator at this object's first such call, kept for its life, so ``torch.manual_seed`` reproduces a run.  Draw:
+        0x80000000 | k, k counting this object's earlier counted calls under the current seed.  ``noise_seed`` / ``noise_draw`` override either and
+        leave the counter alone when both are given.  The counter is plain Python state: it is NOT in the state dict, a resumed run starts at k = 0."""
+        seed = noise_seed
+        if seed is None:
+            seed = cfg.get("noise_seed")
+            if seed is not None:
+                dist = torch.distributed
+                seed = int(seed) + (dist.get_rank() if dist.is_available() and dist.is_initialized() else 0)
+            else:
+                if self.__dict__.get("_loss_own_seed") is None:
+                    lo, hi = torch.randint(0, 1 << 32, (2,), dtype=torch.int64).tolist()
+                    self.__dict__["_loss_own_seed"] = (hi << 32) | lo
+                seed = self.__dict__["_loss_own_seed"]
+        seed = int(seed) & _U64
+        if noise_draw is not None:
+            return seed, int(noise_draw)
+        at, k = self.__dict__.get("_loss_draws", (None, 0))
+        k = k if at == seed else 0
+        if k >= _LOSS_DRAW_BASE:
+            raise RuntimeError("noise_source='device': 2^31 loss draws under one seed are used up; set another test_cfg / train_cfg 'noise_seed'")
+        self.__dict__["_loss_draws"] = (seed, k + 1)
+        return seed, _LOSS_DRAW_BASE | k
+
+    def _forward_train_device(self, x_0, t, seed, draw, concat_cond, grad_guide_fn, x_t_detach):
+        """the prior loss on device noise.  Fused route (V mode, no guidance, no conditioning, fp32 latent with n_per % 4 == 0, ``use_fused_step``):
+        ``ssdnerf_prior_q_sample`` -> UNet -> ``ssdnerf_prior_loss_v`` (fp32 or bf16 output), the noise never in memory; everything else -- and a UNet
+        output of another dtype -- goes through the tensor expressions of the host path on ``_device_noise``: the same normals, bit for bit."""
+        B = x_0.size(0)
+        v_loss = hasattr(self.ddpm_loss, "forward_msd") and self.ddpm_loss.data_info == dict(pred="v_t_pred", target="v_t")
+        fused = (self.use_fused_step and self.denoising_mean_mode.upper() == "V" and v_loss and grad_guide_fn is None and concat_cond is None
+                 and x_0.is_cuda and x_0.dtype == torch.float32 and B > 0 and (x_0.numel() // B) % 4 == 0)
+        if not fused:
+            return None
+        ab = self.schedule.signal_noise(x_0.device)[:, t]
+        a, b = ab[0].contiguous(), ab[1].contiguous()
+        x_0 = x_0.contiguous()
+        x_t = _PriorQSample.apply(x_0.detach() if x_t_detach else x_0, a, b, seed, draw)
+        out = self.denoising(x_t, t, concat_cond=None)
+        if out.dtype in _PRIOR_DTYPES:
+            msd, x0sq = _PriorLossV.apply(out.contiguous(), x_0, a, b, seed, draw)
+            return self.ddpm_loss.forward_msd(msd, t, x0sq)
+        return self.loss(out, x_0, _device_noise(x_0, seed, draw), t, a.reshape(-1, 1, 1, 1), b.reshape(-1, 1, 1, 1))
+
+    def forward_train(self, x_0, concat_cond=None, grad_guide_fn=None, cfg=dict(), x_t_detach=False, timesteps=None, noise=None, noise_seed=None,
+                      noise_draw=None, **kwargs):
         """Diffusion prior loss of ``x_0`` (gaussian_diffusion.py:407-433).  ``timesteps`` / ``noise`` (extra): injected draws; by default both
         are drawn on the host like the reference's, so seeding reproduces them on any device.  ``log_vars['loss_ddpm_mse']`` is a detached
-        0-dim tensor, not a Python float (no device sync here)."""
+        0-dim tensor, not a Python float (no device sync here).
+        ``cfg['noise_source'] = 'device'`` (opt-in; ``train_step`` hands in ``train_cfg``, ``val_optim`` and ``_refine_under_prior`` ``test_cfg``): the
+        noise comes from the counter-based generator under ``_loss_draw``'s (seed, draw) -- ``noise_seed`` / ``noise_draw`` (extra) name them for tests
+        and parity runs -- and the loss around the UNet runs in the kernels of csrc/prior_loss.hip (``_forward_train_device``).  Timesteps stay the
+        sampler's host draw; an injected ``noise`` always wins."""
         assert x_0.dim() == 4
         dev = x_0.device
+        source = cfg.get("noise_source", "host")
+        if source not in ("host", "device"):
+            raise ValueError(f"cfg['noise_source'] must be 'host' or 'device', not {source!r}")
+        if noise is None and (source == "device" or noise_seed is not None):
+            _require_device_latent(x_0)
+            t = (self.sampler(x_0.size(0)) if timesteps is None else torch.as_tensor(timesteps).long()).to(dev)
+            seed, draw = self._loss_draw(cfg, noise_seed, noise_draw)
+            value = self._forward_train_device(x_0, t, seed, draw, concat_cond, grad_guide_fn, x_t_detach)
+            if value is not None:
+                log_vars = self.ddpm_loss.log_vars
+                log_vars.update(loss_ddpm_mse=value.detach())
+                return value, log_vars
+            noise, timesteps = _device_noise(x_0, seed, draw), t
         t = (self.sampler(x_0.size(0)) if timesteps is None else torch.as_tensor(timesteps).long()).to(dev)
         noise = (_host_noise(x_0) if noise is None else noise).to(dev)
         x_t, a, b = self.q_sample(x_0, t, noise)

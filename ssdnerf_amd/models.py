@@ -778,7 +778,9 @@ class DiffusionNeRF(MultiSceneNeRF):
                 sch = self.build_scheduler(opt, cfg)
                 inner_cfg = dict(cfg, n_inverse_steps=extra + 1)
                 from .diffusion import _host_noise
-                next_noise, rng_after_prefetch, prefetch_ok = None, None, True
+                # test_cfg['noise_source'] = 'device': the loss makes its noise in its own kernels (diffusion.forward_train) -- no host draw to hide, so no
+                # prefetch, no generator-state comparison and no warning
+                next_noise, rng_after_prefetch, prefetch_ok = None, None, cfg.get("noise_source", "host") != "device"
                 for k in range(n_outer):
                     opt.zero_grad()
                     # (r04 advisor) the prefetch keeps the reference's order of host draws only while nothing else draws from torch's CPU generator between the

@@ -17,6 +17,7 @@ ap.add_argument("--extra-scene-step", type=int, default=3); ap.add_argument("--d
 ap.add_argument("--full-batch", action="store_true", help="also time (and with --cprofile: profile the host side of) ONE whole val_step: 75 guided steps + 25 x (1 + 4) + 250 views")
 ap.add_argument("--cprofile", action="store_true", help="cProfile of the timed fine-tuning call (host side: top functions by own time)")
 ap.add_argument("--aten", action="store_true", help="with --profile: the aten:: operators with device time by input shape (copies, fills, accumulations outside the custom kernels)")
+ap.add_argument("--noise-source", default="host", choices=["host", "device"], help="where the prior loss of the fine-tuning iteration (and any noise-injecting sampling step) takes its noise from: test_cfg['noise_source'] (DESIGN.md sections 22 and 24)")
 ap.add_argument("--profile", action="store_true", help="instead of timing: torch.profiler tables (top kernels by device time) of one guided step and one outer iteration")
 a = ap.parse_args()
 cfg = dict(type="DiffusionNeRF", code_size=(3, 6, 128, 128), code_reshape=(18, 128, 128), code_activation=dict(type="TanhCode", scale=2), grid_size=64,
@@ -43,6 +44,9 @@ with torch.no_grad():
         p.copy_(torch.randn(p.shape, generator=g) * 0.02)
 model.decoder_ema.load_state_dict(S.make_decoder_params(), strict=False)
 model = model.cuda().eval()
+if a.noise_source != "host":                                                  # (the default leaves both dictionaries as every earlier figure had them)
+    model.test_cfg.update(noise_source=a.noise_source, noise_seed=0)
+    model.diffusion_ema.test_cfg.update(noise_source=a.noise_source, noise_seed=0)
 ns = a.scenes
 codes = torch.stack([S.make_triplane(100 + i) for i in range(ns)]).cuda()
 poses = S.spiral_poses()[[64]].cuda()[None].expand(ns, -1, -1, -1).contiguous()
@@ -81,7 +85,7 @@ if a.profile:
         print(prof.key_averages().table(sort_by="self_cuda_time_total", row_limit=28, max_name_column_width=70))
     sys.exit(0)
 
-out = dict(scenes=ns, unet_dtype=a.dtype)
+out = dict(scenes=ns, unet_dtype=a.dtype, noise_source=a.noise_source)
 # guidance: time k and 1 step runs, the difference is the per-step cost without the fixed setup
 unet = model.diffusion_ema.denoising
 model.test_cfg["num_timesteps"] = model.diffusion_ema.test_cfg["num_timesteps"] = 2 + int(getattr(unet, "grad_graph_after", 0))
