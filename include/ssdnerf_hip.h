@@ -267,7 +267,10 @@ int ssdnerf_render_shade_queue_mfma_cams(const void* planes, int planes_dtype, u
 /* Fused full-refresh branch of BaseNeRF.update_extra_state (base_nerf.py:328-351,377-387) for S scenes:
  * for every cell of the H^3 grid (x-major order like custom_meshgrid) decode sigma at the jittered cell centre
  * (jitter [H^3,3] uniform [0,1) shared by all scenes as in the reference, or NULL for no jitter) and fold it
- * into density_grid [S,H^3] (Morton order, dtype grid_dtype): g = (g>=0) ? max(g*decay, sigma) : g.
+ * into density_grid [S,H^3] (Morton order, dtype grid_dtype): g = (g>=0 && sigma is not NaN) ? max(g*decay, sigma) : g,
+ * sigma clamped to the dtype's largest finite value.  grid_size must be a power of two in [2, 1024]: a cell's Morton
+ * index stays below H^3 only then, and H^3 is a multiple of 8 for the bitfield; any other size is refused with
+ * SSDNERF_E_INVALID before anything is launched.
  * mean_out [1] fp32 (optional) receives mean(max(g,0)) over all S*H^3 cells (caller zero-initialises; it is
  * accumulated with atomics), which the reference turns into the packbits threshold. */
 int ssdnerf_density_grid_update(const void* planes, int planes_dtype, uint32_t Hp, uint32_t Wp, const float* mlp_params,

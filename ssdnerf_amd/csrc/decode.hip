@@ -948,8 +948,15 @@ __global__ void __launch_bounds__(DEC_TPB) k_density_update(const PT* __restrict
         const float old = ssd_grid_ld<GT>(cellp);
         const float fresh = ssd_grid_rt<GT>(fminf(sigma, ssd_grid_max<GT>()));
         float out = old;
-        if (old >= 0.0f && fresh >= 0.0f) {
-            const float decayed = ssd_grid_rt<GT>(old * decay);  // product rounded to the grid dtype first
+        // fminf returns its other operand for a NaN: the NaN of a sample whose footprint holds a NaN texel is tested on sigma itself, so that such a
+        // cell keeps its value (the reference's ~isnan(tmp_grid)) instead of being set to the dtype's largest value
+        if (old >= 0.0f && sigma == sigma && fresh >= 0.0f) {
+            // the fp32 product, THEN the rounding to the grid dtype (torch's fp16 tensor times a scalar).  The empty asm pins the product in a register:
+            // without it the compiler selects v_fma_mixlo_f16 for the pair, which rounds the exact product once, straight to fp16 -- another value
+            // for one fp16 input in 23 at decay 0.9 (tests/test_density_fp64_gpu.py)
+            float prod = old * decay;
+            asm volatile("" : "+v"(prod));
+            const float decayed = ssd_grid_rt<GT>(prod);
             out = fmaxf(decayed, fresh);
             *cellp = ssd_grid_round<GT>(out);
         }
@@ -979,7 +986,9 @@ extern "C" int ssdnerf_density_grid_update(const void* planes, int planes_dtype,
     if (S == 0) return SSDNERF_OK;  // empty input: nothing to do (pointers may be null)
     SSD_REQUIRE(planes && mlp_params && density_grid, "density_grid_update: null pointer");
     SSD_REQUIRE((planes_dtype == 0 || planes_dtype == 1) && (grid_dtype == 0 || grid_dtype == 1), "density_grid_update: unsupported dtype");
-    SSD_REQUIRE(grid_size >= 1 && grid_size <= 1024, "density_grid_update: grid_size out of range");
+    // cell (cx, cy, cz) is written at its Morton index, which stays below grid_size^3 only for a power of two; from 2 on, grid_size^3 is a multiple of 8 (packbits)
+    SSD_REQUIRE(grid_size >= 2 && grid_size <= 1024 && (grid_size & (grid_size - 1)) == 0,
+                "density_grid_update: grid_size %u is not a power of two in [2, 1024]", grid_size);
     const PlaneGeom g = ssd_plane_geom(Hp, Wp);
     const uint32_t H3 = grid_size * grid_size * grid_size;
     const float centre = (float)((double)(grid_size - 1) / 2.0);

@@ -17,10 +17,12 @@ def update_density_grid(decoder: TriPlaneDecoder, code: torch.Tensor, density_gr
                         planes: Optional[torch.Tensor] = None, return_thresh: bool = True):
     """In place on ``density_grid`` (S,H^3; fp16 or fp32, Morton order) and ``density_bitfield`` (S,H^3/8 uint8).
     ``jitter`` (H^3,3) in [0,1) is the reference's ``torch.rand_like`` draw, shared by all scenes; None draws it here."""
-    assert decoder.fused_supported(code), "update_density_grid needs the fused-decode configuration"
     s, h3 = density_grid.shape
     h = round(h3 ** (1 / 3))
-    assert h ** 3 == h3
+    if h ** 3 != h3 or h < 2 or h > 1024 or h & (h - 1):
+        # the kernel writes a cell at its Morton index, which stays inside the grid only for a power of two: refused before anything is allocated or launched
+        raise ValueError(f"update_density_grid: a density grid of {h3} cells per scene is not the cube of a power of two in [2, 1024]")
+    assert decoder.fused_supported(code), "update_density_grid needs the fused-decode configuration"
     dev = code.device
     if planes is None:
         planes = pack_triplanes(code.detach(), decoder.plane_dtype)

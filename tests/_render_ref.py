@@ -135,14 +135,17 @@ def _foot(ix, size):
     return i0, i1, 1.0 - w1, w1
 
 
-def gather18(code, xyz):
+def gather18(code, xyz, pos_unc=None):
     """(f [N, 18], B_f [N, 18]): f[c * 3 + p] = bilinear sample of channel c of plane p of ``code`` (3, 6, H, W; fp32, or fp16 values for fp16 planes).
       chain:       C_CHAIN u sum |t w|                                                                                         (C_CHAIN above)
       coordinates: each fractional coordinate is uncertain by C_X u size texels (C_X above); df/dix = wy0 (t01 - t00) + wy1 (t11 - t10) and likewise in y,
                    so the feature moves by at most that many texels times the absolute corner differences of the footprint.  A coordinate within its
                    uncertainty of a texel centre may fall into the neighbouring cell, whose slope is another: the slope is taken as the larger of the two
                    evaluated at ix -/+ the uncertainty.  The bilinear blend is continuous and the clamp 1-Lipschitz, so nothing else happens at cell or
-                   plane borders.  Where the footprint's texels are equal the term is exactly 0."""
+                   plane borders.  Where the footprint's texels are equal the term is exactly 0.
+      ``pos_unc`` [N, 3] (optional): an uncertainty of the sample position itself, per axis, in units of the position -- for a kernel that forms the
+                   position and does not output it (tests/_density_ref.py).  ix = ((u + 1) size - 1) / 2 moves by size / 2 texels per unit: pos_unc size / 2
+                   is added to the coordinate uncertainty.  None leaves every number as it was."""
     code, xyz = _np64(code), _np64(xyz).reshape(-1, 3)
     N, (H, W) = len(xyz), code.shape[2:]
     f, Bf = np.zeros((N, 18)), np.zeros((N, 18))
@@ -157,6 +160,11 @@ def gather18(code, xyz):
             return t, (wx0[:, None], wx1[:, None], wy0[:, None], wy1[:, None])
 
         ix, iy = _coord(xyz[:, a], W), _coord(xyz[:, b], H)
+        if pos_unc is None:
+            dx, dy, dxc, dyc = dix, diy, dix, diy
+        else:
+            dx, dy = dix + 0.5 * W * _np64(pos_unc)[:, a], diy + 0.5 * H * _np64(pos_unc)[:, b]
+            dxc, dyc = dx[:, None], dy[:, None]
         (t00, t01, t10, t11), (wx0, wx1, wy0, wy1) = tap(ix, iy)
         val = t00 * (wx0 * wy0) + t01 * (wx1 * wy0) + t10 * (wx0 * wy1) + t11 * (wx1 * wy1)
         mag = np.abs(t00) * (wx0 * wy0) + np.abs(t01) * (wx1 * wy0) + np.abs(t10) * (wx0 * wy1) + np.abs(t11) * (wx1 * wy1)
@@ -171,8 +179,8 @@ def gather18(code, xyz):
 
         cols = np.arange(6) * 3 + p
         f[:, cols] = val
-        Bf[:, cols] = (C_CHAIN * U32 * mag + dix * np.maximum(slope_x(ix - dix), slope_x(ix + dix))
-                       + diy * np.maximum(slope_y(iy - diy), slope_y(iy + diy)))
+        Bf[:, cols] = (C_CHAIN * U32 * mag + dxc * np.maximum(slope_x(ix - dx), slope_x(ix + dx))
+                       + dyc * np.maximum(slope_y(iy - dy), slope_y(iy + dy)))
     return f, Bf
 
 
@@ -204,10 +212,11 @@ def sigmoid_terms(h, Bh):
 
 
 # ------------------------------------------------------------------------------------------------ per sample
-def decode_terms(P, code, xyz, dirs, sat, mfma, density_only=False):
+def decode_terms(P, code, xyz, dirs, sat, mfma, density_only=False, pos_unc=None):
     """``ssd_mlp`` on ``ssd_gather18``'s features in float64, every quantity with its carried bound, as a namespace: the outputs sigma [N], B_sigma, rgb [N, 3], B_rgb
     (what ``decode_ref`` returns) and the features f, pre-activations h, h + d (``hc``), sa, z with B_f, B_h, B_hc, B_sa, B_z and the layer magnitudes S1, Sd, which
     the decode gradient's reference (tests/_decode_grad_ref.py) starts from.  ``mfma`` may also be a dict of another kernel's layer allowances (see below).
+    ``pos_unc``: ``gather18``'s optional position uncertainty.
         h = W1 f + b1;  sigma = exp(w_sigma . silu(h) + b_sigma);  rgb = sigmoid(Wc silu(h + Wd SH4(d) + bd) + bc) (1 + 2 sat) - sat.
     Bounds, S_* = sum of the magnitudes of a layer's terms and its bias, B_* carried:
       h:       |W1| B_f + K_BASE u S_1                                        MFMA: (K_BASE_MFMA + SPLIT + PRESCALE) u S_1
@@ -217,7 +226,7 @@ def decode_terms(P, code, xyz, dirs, sat, mfma, density_only=False):
       sigma:   relative: B_sa (1 + B_sa) carried, |sa| u for fl(sa log2e), C_EXP u for the exp2 unit
       rgb:     k = fl(1 + 2 sat) rounds once (u k sigmoid), the fma once (u |rgb|), the sigmoid's bound is scaled by k"""
     p = unpack_params(P)
-    f, Bf = gather18(code, xyz)
+    f, Bf = gather18(code, xyz, pos_unc)
     aW1 = np.abs(p.W1)
     h, S1 = f @ p.W1.T + p.b1, np.abs(f) @ aW1.T + np.abs(p.b1)
     own = mfma if isinstance(mfma, dict) else None      # another kernel's layer allowances {"base", "dir", "out"}, in the VALU class's shape (tests/_decode_grad_ref.py)
