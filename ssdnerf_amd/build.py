@@ -33,7 +33,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("SSDNERF_LIB_DIR") or os.path.join(HERE, "lib")     # SSDNERF_LIB_DIR + SSDNERF_EXTRA_FLAGS: side builds for A/B runs
 LIB_PATH = os.path.join(LIB_DIR, "libssdnerf_hip.so")
-SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "sampler_step.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip", "mesh_attr.hip", "lpips.hip", "feature_stats.hip", "adam.hip", "scene_store.hip", "ema.hip", "scene_cache.hip", "png_rows.hip", "prior_loss.hip"]
+SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "decode_bwd.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "sampler_step.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip", "mesh_attr.hip", "lpips.hip", "feature_stats.hip", "adam.hip", "scene_store.hip", "ema.hip", "scene_cache.hip", "png_rows.hip", "prior_loss.hip"]
 LLVM_BIN = os.environ.get("SSDNERF_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TRANS_USE_WAIT_STATES = int(os.environ.get("SSDNERF_TRANS_USE_WAIT_STATES", "1"))     # 1 = the toolchain's own distance: the r03 rule is off (r06)
 SWAP_MFMA_WAIT_STATES = int(os.environ.get("SSDNERF_SWAP_MFMA_WAIT_STATES", "0"))    # asm_postpass.SWAP_MFMA_WAIT_STATES (0 = rule off: the default since r06)

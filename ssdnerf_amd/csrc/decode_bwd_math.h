@@ -15,7 +15,7 @@
 // Nothing is saved by the forward: the 64 hidden units are recomputed twice here (once to reach the outputs, once to push the
 // gradient back), ~5.5 kFMA per point, instead of storing 2 x 64 floats per point.
 //
-// The file is plain C on purpose: the device kernel (decode.hip) and a gcc-built host harness (tests/host/decode_bwd_host.c, which
+// The file is plain C on purpose: the device kernel (decode_bwd.hip) and a gcc-built host harness (tests/host/decode_bwd_host.c, which
 // the CPU test checks against PyTorch autograd) compile the SAME arithmetic.  Parameter block layout: decode_core.h.
 #pragma once
 #include <math.h>
@@ -42,7 +42,7 @@
 SSDB_FN float ssdb_sigmoid(float u) { return SSDB_RCP(1.0f + SSDB_EXP2(u * -1.4426950408889634f)); }
 
 // unnormalise + clip one coordinate exactly as the forward gather does (decode_core.h ssd_grid_coord), in two halves so that the binned
-// reduction of decode.hip can store the clipped coordinate between them
+// reduction of decode_bwd.hip can store the clipped coordinate between them
 SSDB_FN float ssdb_unnormalise(float u, uint32_t size) {
     const float size_f = (float)size;
     const float ix = ((u + 1.0f) * size_f - 1.0f) * 0.5f;

@@ -429,7 +429,7 @@ class TriPlaneDecoder(VolumeRenderer):
 
     #: SSDNERF_DECODE_GRAD=0 sends the code-gradient decode through PyTorch autograd (grid_sample + nn.Linear) instead of the fused kernels
     fused_code_grad = os.environ.get("SSDNERF_DECODE_GRAD", "1") != "0"
-    #: r06, opt-in (SSDNERF_DECODE_BWD_FEAT_MFMA=1): the decode backward's per-sample feature gradients on the matrix cores (csrc/decode.hip: k_decode_bwd_feat_mfma; bf16-pair
+    #: r06, opt-in (SSDNERF_DECODE_BWD_FEAT_MFMA=1): the decode backward's per-sample feature gradients on the matrix cores (csrc/decode_bwd.hip: k_decode_bwd_feat_mfma; bf16-pair
     #: products instead of fp32 FMAs).  Measured: 1.55 -> 1.27 ms on 7 M march-ordered samples, 1.60 -> 1.56 ms on uniformly scattered ones (the gather and the compaction are
     #: 0.4 - 0.6 ms of either), guided step -0.1 ms: not worth a lower arithmetic class by default.
     decode_bwd_feat_mfma = os.environ.get("SSDNERF_DECODE_BWD_FEAT_MFMA", "0") == "1"

@@ -1,4 +1,4 @@
-"""float64 reference of the decode gradient -- ``ssdnerf_point_decode_backward`` (csrc/decode.hip): ``k_decode_bwd_feat`` (or the opt-in
+"""float64 reference of the decode gradient -- ``ssdnerf_point_decode_backward`` (csrc/decode_bwd.hip): ``k_decode_bwd_feat`` (or the opt-in
 ``k_decode_bwd_feat_mfma``), ``k_decode_bwd_bin_owned``, ``k_decode_bwd_sum`` -- with error bounds derived from the kernels' arithmetic, and the seeded
 case families of tests/test_decode_grad_bounds_cpu.py (the bounds accept fp32 evaluations of the same arithmetic and reject subtly wrong ones) and
 tests/test_decode_grad_fp64_gpu.py (the kernels meet them).  Built on tests/_render_ref.py: its gather, SH, activations, the forward's carried
@@ -301,7 +301,7 @@ def _dirs(rng, n):
 
 
 def pair_residual(x):
-    """x - hi - lo of ``db_split_pair`` (csrc/decode.hip): hi = bf16(x), lo = bf16(x - hi), both rounded to nearest even, for fp32 values"""
+    """x - hi - lo of ``db_split_pair`` (csrc/decode_bwd.hip): hi = bf16(x), lo = bf16(x - hi), both rounded to nearest even, for fp32 values"""
     def bf16(v):
         b = np.asarray(v, np.float32).view(np.uint32).astype(np.uint64)
         return (((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)

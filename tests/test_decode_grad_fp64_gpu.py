@@ -1,4 +1,4 @@
-"""``ssdnerf_point_decode_backward`` (csrc/decode.hip) against the float64 reference and the derived bounds of tests/_decode_grad_ref.py, on the seeded families that
+"""``ssdnerf_point_decode_backward`` (csrc/decode_bwd.hip) against the float64 reference and the derived bounds of tests/_decode_grad_ref.py, on the seeded families that
 tests/test_decode_grad_bounds_cpu.py proves the bounds on.  The pipeline is split at the workspace (``ssdnerf_point_decode_backward_layout``): the tests call the
 C ABI with a workspace tensor of their own and read the intermediates back.
   * per sample: ``counters`` are exact, every slot is identified through its keys and every sample with a gradient is present exactly once, ``pos`` is within the
@@ -9,7 +9,6 @@ C ABI with a workspace tensor of their own and read the intermediates back.
   * end to end: ``TriPlaneDecoder.point_decode`` + ``torch.autograd.grad`` (``_PointDecodeFn``: cached workspace, offsets from the point counts) under the end-to-end
     per-texel bound, also for a smaller problem behind a larger one on the same decoder (stale workspace contents).
 The control runs the MFMA variant against the VALU bound on the coherent family.
-Out of scope: the LDS-atomics A/B kernel ``k_decode_bwd_bin`` -- it is selected by an environment variable read once per process and is not dispatched by default.
 The per-sample bounds are worst-case (coordinate uncertainty C_X u size on every gather, u times the partial sums of every chain, carried through 64 hidden units):
 on random planes, where the coordinate term leads, the default kernel sits at 0.01 - 0.03 of them (profiles/decode_grad_bounds.json), like ``point_decode``'s
 colours under the forward's, and at 0.10 on the coherent family; the reduction bound is met at up to ~0.5.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """tools/bench_decode_bwd.py -- ssdnerf_point_decode_backward alone on synthetic samples (fog-like: uniform in the box), the guidance
 workload's shape: --scenes x --samples points, every point with a gradient.  Prints ms per call (HIP events); run it under
-`rocprofv3 --kernel-trace --stats` for the per-kernel split (k_decode_bwd_feat / _bin / _sum)."""
+`rocprofv3 --kernel-trace --stats` for the per-kernel split (k_decode_bwd_feat / _bin_owned / _sum)."""
 import argparse, json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
