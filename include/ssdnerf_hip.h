@@ -175,6 +175,22 @@ int ssdnerf_point_decode_backward(const void* planes, int planes_dtype, uint32_t
                                   float sigmoid_saturation, const float* grad_sigmas, const float* grad_rgbs, float* grad_code,
                                   void* workspace, size_t workspace_bytes, void* stream);
 
+/* Gradient of ssdnerf_point_decode w.r.t. the DECODER's parameters -- what autograd does through the four nn.Linear layers when the rendering loss is differentiated
+ * with a trainable decoder (the closing iteration of a training step: multiscene_nerf.py, loss_decoder + backward) -- for ALL scenes of a batch.  Inputs as
+ * ssdnerf_point_decode_backward (planes fp32 or fp16; colour and density heads together: dirs and grad_rgbs are required, grad_sigmas may be NULL) ->
+ * grad_params [SSDNERF_MLP_PARAM_FLOATS] fp32 in the PACKED layout of mlp_params (Wc transposed into the records, the unused column rec[:, 23] exactly 0),
+ * OVERWRITTEN.  No gradient flows to positions or directions.  Samples with an all-zero upstream gradient contribute nothing; total == 0 gives all zeros.
+ * The sum over the samples is formed WITHOUT floating-point atomics and in a fixed order -- persistent blocks over 256-sample groups (group g -> block g mod blocks),
+ * per-lane register accumulators, the block's waves in wave order, one record per block in the workspace, then the records in block order: two calls on the same
+ * inputs with the same max_blocks give the same bits.  Plain fp32 fused multiply-adds.  max_blocks: upper limit of the block count (0 = default, two per compute
+ * unit); a small value makes few blocks loop over many groups.  workspace: ssdnerf_point_decode_backward_params_workspace bytes (one record per block). */
+size_t ssdnerf_point_decode_backward_params_workspace(uint32_t S, uint32_t total, uint32_t max_blocks);
+int ssdnerf_point_decode_backward_params(const void* planes, int planes_dtype, uint32_t S, uint32_t Hp, uint32_t Wp, const float* mlp_params,
+                                         const float* xyzs, const float* dirs, const uint32_t* offsets, uint32_t total,
+                                         float sigmoid_saturation, const float* grad_sigmas, const float* grad_rgbs,
+                                         float* grad_params /* SSDNERF_MLP_PARAM_FLOATS, packed layout */, uint32_t max_blocks /* 0 = default, 2 per CU */,
+                                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* Fused eval-branch render of VolumeRenderer.forward (base_volume_renderer.py:79-123) + the background blend
  * of BaseNeRF.render (base_nerf.py:522-523) for ONE scene: AABB -> bitfield-guided march -> gather -> MLP ->
  * composite entirely on chip.  rays_o/rays_d [N,3] in, image [N,3] (already blended with bg_color), depth [N],

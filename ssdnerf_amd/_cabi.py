@@ -27,6 +27,7 @@ EXPORTS = [
     "ssdnerf_composite_rays_train_forward", "ssdnerf_composite_rays_train_backward", "ssdnerf_march_rays", "ssdnerf_composite_rays",
     "ssdnerf_sh_encode_forward", "ssdnerf_sh_encode_backward", "ssdnerf_triplane_pack", "ssdnerf_point_decode", "ssdnerf_point_decode_backward_workspace",
     "ssdnerf_point_decode_backward", "ssdnerf_point_decode_backward_layout",
+    "ssdnerf_point_decode_backward_params_workspace", "ssdnerf_point_decode_backward_params",
     "ssdnerf_render_rays_fused", "ssdnerf_render_rays_fused_batch", "ssdnerf_render_queue_workspace", "ssdnerf_render_first_hit",
     "ssdnerf_render_shade_queue", "ssdnerf_render_shade_queue_mfma", "ssdnerf_render_first_hit_cams", "ssdnerf_render_shade_queue_mfma_cams", "ssdnerf_density_grid_update", "ssdnerf_packbits_dev_thresh", "ssdnerf_ddim_step_v",
     "ssdnerf_group_norm_workspace", "ssdnerf_group_norm_backward_workspace", "ssdnerf_group_norm_nhwc", "ssdnerf_group_norm_nhwc_runs", "ssdnerf_group_norm_nhwc_backward", "ssdnerf_group_norm_nhwc_backward_cat", "ssdnerf_bias_residual_nhwc",
@@ -96,6 +97,10 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_point_decode_backward_workspace.argtypes = [ctypes.c_uint32] * 4
         l.ssdnerf_point_decode_backward_layout.restype = None
         l.ssdnerf_point_decode_backward_layout.argtypes = [ctypes.c_uint32] * 4 + [ctypes.POINTER(ctypes.c_uint64)]
+        l.ssdnerf_point_decode_backward_params_workspace.restype = ctypes.c_size_t
+        l.ssdnerf_point_decode_backward_params_workspace.argtypes = [ctypes.c_uint32] * 3
+        l.ssdnerf_point_decode_backward_params.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4 + \
+                                                          [ctypes.c_uint32, ctypes.c_float] + [ctypes.c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]
         l.ssdnerf_group_norm_workspace.restype = ctypes.c_size_t
         l.ssdnerf_group_norm_workspace.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
         l.ssdnerf_group_norm_backward_workspace.restype = ctypes.c_size_t

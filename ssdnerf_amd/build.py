@@ -33,13 +33,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB_DIR = os.environ.get("SSDNERF_LIB_DIR") or os.path.join(HERE, "lib")     # SSDNERF_LIB_DIR + SSDNERF_EXTRA_FLAGS: side builds for A/B runs
 LIB_PATH = os.path.join(LIB_DIR, "libssdnerf_hip.so")
-SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "decode_bwd.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "sampler_step.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip", "mesh_attr.hip", "lpips.hip", "feature_stats.hip", "adam.hip", "scene_store.hip", "ema.hip", "scene_cache.hip", "png_rows.hip", "prior_loss.hip"]
+SOURCES = ["raymarching_ops.hip", "shencoder.hip", "decode.hip", "decode_bwd.hip", "decode_bwd_params.hip", "render_fused.hip", "render_queue.hip", "shade_mfma.hip", "sampler_step.hip", "groupnorm.hip", "conv_igemm.hip", "attention.hip", "raygen.hip", "marching_cubes.hip", "metrics.hip", "tv_loss.hip", "mesh_attr.hip", "lpips.hip", "feature_stats.hip", "adam.hip", "scene_store.hip", "ema.hip", "scene_cache.hip", "png_rows.hip", "prior_loss.hip"]
 LLVM_BIN = os.environ.get("SSDNERF_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 TRANS_USE_WAIT_STATES = int(os.environ.get("SSDNERF_TRANS_USE_WAIT_STATES", "1"))     # 1 = the toolchain's own distance: the r03 rule is off (r06)
 SWAP_MFMA_WAIT_STATES = int(os.environ.get("SSDNERF_SWAP_MFMA_WAIT_STATES", "0"))    # asm_postpass.SWAP_MFMA_WAIT_STATES (0 = rule off: the default since r06)
 UNPACK_CROSS_HALF = os.environ.get("SSDNERF_KEEP_PACKED_CROSS_HALF", "0") != "1"      # r06 (asm_postpass.unpack_cross_half); =1 keeps the compiler's instructions (positive-control builds)
 VALU_MFMA_WAIT_STATES = int(os.environ.get("SSDNERF_VALU_MFMA_WAIT_STATES", "0"))    # asm_postpass.VALU_MFMA_WAIT_STATES (r06; 0 = rule off)
-HEADERS = ["common.h", "sh_basis.h", "decode_core.h", "decode_bwd_math.h", "gn_bwd_math.h", "adam_math.h", "ema_math.h", "cache_cvt.h", "philox.h", "keyed_perm.h", os.path.join("..", "..", "include", "ssdnerf_hip.h")]
+HEADERS = ["common.h", "sh_basis.h", "decode_core.h", "decode_bwd_math.h", "decode_bwd_params_math.h", "gn_bwd_math.h", "adam_math.h", "ema_math.h", "cache_cvt.h", "philox.h", "keyed_perm.h", os.path.join("..", "..", "include", "ssdnerf_hip.h")]
 VALIDATED_HIP_VERSIONS = ("7.2.",)              # prefixes of `hipcc --version`'s "HIP version:" the post-pass + hazard analysis were validated on (r03 / r04)
 FLAGS = os.environ.get("SSDNERF_EXTRA_FLAGS", "").split() + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-result"]
 # per-source additions: OCML's powf, SLP-vectorised, leaves a packed fp32 add whose halves overwrite each other's source (the post-pass cannot

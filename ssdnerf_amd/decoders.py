@@ -9,7 +9,8 @@ fast path behind them:
 * ``point_decode`` / ``point_density_decode`` on packed sample lists -> one fused HIP decode per scene; when only the
   scene code needs a gradient (guidance, fine-tuning) the backward is fused too (``_PointDecodeFn``: re-gather +
   recomputed MLP + atomic scatter); an eager PyTorch-ROCm path remains for decoder-parameter gradients (autograd;
-  also the "reference-shaped eager" baseline B1).
+  also the "reference-shaped eager" baseline B1), unless ``param_grad='fused'`` opts into ``_PointDecodeParamFn``: the fused
+  forward and the parameter gradients of csrc/decode_bwd_params.hip.
 * train branch -> per-scene ``march_rays_train`` (deterministic prefix-sum packing) + decode +
   ``batch_composite_rays_train`` (HIP forward/backward kernels).
 
@@ -120,6 +121,68 @@ class _PointDecodeFn(torch.autograd.Function):
             C.ptr(offsets), C.u32(total), C.f32(decoder.sigmoid_saturation), C.ptr(g_sigmas), C.ptr(g_rgbs), C.ptr(grad_code), C.ptr(ws),
             C.ctypes.c_size_t(ws_bytes), C.stream()), "point_decode_backward")
         return grad_code.to(dtype), None, None, None
+
+
+class _PointDecodeParamFn(torch.autograd.Function):
+    """Fused point decode, differentiable w.r.t. the scene code AND the decoder's eight parameter tensors (``param_grad='fused'``: the closing joint iteration of a
+    training step).  forward = ``_PointDecodeFn``'s, on ``packed_params()``; backward = ONE ``ssdnerf_point_decode_backward_params`` for the whole batch (re-gather,
+    recomputed hidden units, the sum over the samples in per-lane registers, no atomics, fixed order: bit-reproducible), whose packed gradient is sliced back into the
+    eight tensors, and -- only when the code needs a gradient -- the unchanged ``ssdnerf_point_decode_backward``.  The parameter tensors are inputs so that autograd
+    routes their gradients; the kernels read the packed block."""
+
+    @staticmethod
+    def forward(ctx, code, w1, b1, ws, bs, wd, bd, wc, bc, decoder, xyzs, dirs):
+        planes = pack_triplanes(code.detach(), decoder.plane_dtype)
+        xyzs = [x.detach().reshape(-1, 3).float().contiguous() for x in xyzs]
+        dirs = [d.detach().reshape(-1, 3).float().contiguous() for d in dirs]
+        sigmas, rgbs, num_points = decoder._point_decode_hip(xyzs, dirs, code, False, planes=planes)
+        ctx.decoder, ctx.planes, ctx.xyzs, ctx.dirs, ctx.num_points = decoder, planes, xyzs, dirs, num_points
+        ctx.packed = decoder.packed_params()                                   # the block the forward read (an optimizer step before backward re-packs into a new tensor)
+        ctx.code_meta = (code.shape, code.dtype)
+        ctx.param_dtypes = tuple(p.dtype for p in (w1, b1, ws, bs, wd, bd, wc, bc))
+        return sigmas, rgbs
+
+    @staticmethod
+    def backward(ctx, g_sigmas, g_rgbs):
+        decoder, planes, packed = ctx.decoder, ctx.planes, ctx.packed
+        shape, code_dtype = ctx.code_meta
+        s_, _, c, hp, wp = shape
+        assert c == 6, "the fused decode gradient is written for 6-channel planes (18 features)"
+        total = sum(ctx.num_points)
+        dev = planes.device
+        g_sigmas = torch.zeros(total, dtype=torch.float32, device=dev) if g_sigmas is None else g_sigmas.float().contiguous()
+        g_rgbs = torch.zeros(total, 3, dtype=torch.float32, device=dev) if g_rgbs is None else g_rgbs.float().contiguous()
+        xyzs = ctx.xyzs[0] if s_ == 1 else torch.cat(ctx.xyzs, dim=0)
+        dirs = ctx.dirs[0] if s_ == 1 else torch.cat(ctx.dirs, dim=0)
+        bounds = [0]
+        for n in ctx.num_points:
+            bounds.append(bounds[-1] + n)
+        offsets = torch.tensor(bounds, dtype=torch.int32, device=dev)          # (a blocking copy: the host list dies with this frame)
+        lib = C.lib()
+        grads = [None] * 9
+        if any(ctx.needs_input_grad[1:9]):
+            gp = torch.empty(MLP_PARAM_FLOATS, dtype=torch.float32, device=dev)
+            ws_bytes = int(lib.ssdnerf_point_decode_backward_params_workspace(C.u32(s_), C.u32(total), C.u32(0)))
+            ws = decoder._workspace(max(ws_bytes, 1), dev, "decode_bwd_params")
+            C.check(lib.ssdnerf_point_decode_backward_params(
+                C.ptr(planes), C.dtype_code(planes), C.u32(s_), C.u32(hp), C.u32(wp), C.ptr(packed), C.ptr(xyzs), C.ptr(dirs), C.ptr(offsets), C.u32(total),
+                C.f32(decoder.sigmoid_saturation), C.ptr(g_sigmas), C.ptr(g_rgbs), C.ptr(gp), C.u32(0), C.ptr(ws), C.ctypes.c_size_t(ws_bytes), C.stream()),
+                "point_decode_backward_params")
+            rec = gp[:64 * 24].view(64, 24)                                    # the packed layout of csrc/decode_core.h; Wc sits transposed in the records
+            sliced = (rec[:, :18], rec[:, 18], rec[:, 19].unsqueeze(0), gp[2624:2625], gp[1536:2560].view(64, 16), gp[2560:2624], rec[:, 20:23].t(), gp[2625:2628])
+            for i, (g, dt) in enumerate(zip(sliced, ctx.param_dtypes)):
+                if ctx.needs_input_grad[1 + i]:
+                    grads[1 + i] = g.to(dt).contiguous()
+        if ctx.needs_input_grad[0]:
+            grad_code = torch.empty(s_, 3, 6, hp, wp, dtype=torch.float32, device=dev)
+            ws_bytes = int(lib.ssdnerf_point_decode_backward_workspace(C.u32(s_), C.u32(total), C.u32(hp), C.u32(wp)))
+            ws = decoder._workspace(max(ws_bytes, 1), dev, "decode_bwd")
+            C.check(lib.ssdnerf_point_decode_backward(
+                C.ptr(planes), C.dtype_code(planes) | (0x100 if getattr(decoder, "decode_bwd_feat_mfma", False) else 0), C.u32(s_), C.u32(hp), C.u32(wp),
+                C.ptr(packed), C.ptr(xyzs), C.ptr(dirs), C.ptr(offsets), C.u32(total), C.f32(decoder.sigmoid_saturation), C.ptr(g_sigmas), C.ptr(g_rgbs),
+                C.ptr(grad_code), C.ptr(ws), C.ctypes.c_size_t(ws_bytes), C.stream()), "point_decode_backward")
+            grads[0] = grad_code.to(code_dtype)
+        return (*grads, None, None, None)
 
 
 class VolumeRenderer(nn.Module):
@@ -294,8 +357,12 @@ class TriPlaneDecoder(VolumeRenderer):
     def __init__(self, *args, interp_mode="bilinear", base_layers=[3 * 32, 128], density_layers=[128, 1],
                  color_layers=[128, 128, 3], use_dir_enc=True, dir_layers=None, scene_base_size=None, scene_rand_dims=(0, 1),
                  activation="silu", sigma_activation="trunc_exp", sigmoid_saturation=0.001, code_dropout=0.0, flip_z=False,
-                 **kwargs):
+                 param_grad=None, **kwargs):
         super().__init__(*args, **kwargs)
+        if param_grad is not None:                                       # None: the class default (SSDNERF_DECODE_PARAM_GRAD)
+            if param_grad not in ("eager", "fused"):
+                raise ValueError(f"param_grad must be 'eager' or 'fused', got {param_grad!r}")
+            self.param_grad = param_grad
         base_layers, density_layers, color_layers = list(base_layers), list(density_layers), list(color_layers)
         self.interp_mode = interp_mode
         self.in_chn = base_layers[0]
@@ -422,6 +489,14 @@ class TriPlaneDecoder(VolumeRenderer):
                 xyzs, dirs = list(xyzs), list(dirs)
             sigmas, rgbs = _PointDecodeFn.apply(code, self, xyzs, dirs)
             return sigmas, rgbs, [int(x.size(-2)) for x in xyzs]
+        if self.param_grad == "fused" and params_need_grad and not density_only and dirs is not None and self.fused_supported(code):
+            # a trainable decoder (the closing joint iteration of a training step), opted in: fused forward, parameter gradients -- and the code's, when it
+            # needs one -- from the HIP kernels.  Dropout in training, scene_base, other layer shapes and CPU tensors are not ``fused_supported``: eager, below
+            if isinstance(xyzs, torch.Tensor):
+                xyzs, dirs = list(xyzs), list(dirs)
+            ps = [p for m in (self.base_net[0], self.density_net[0], self.dir_net[0], self.color_net[0]) for p in (m.weight, m.bias)]
+            sigmas, rgbs = _PointDecodeParamFn.apply(code, *ps, self, xyzs, dirs)
+            return sigmas, rgbs, [int(x.size(-2)) for x in xyzs]
         return self.point_decode_eager(xyzs, dirs, code, density_only)
 
     #: True forces ``point_decode`` through the eager PyTorch statement (measurement of the reference-shaped path only)
@@ -433,6 +508,10 @@ class TriPlaneDecoder(VolumeRenderer):
     #: products instead of fp32 FMAs).  Measured: 1.55 -> 1.27 ms on 7 M march-ordered samples, 1.60 -> 1.56 ms on uniformly scattered ones (the gather and the compaction are
     #: 0.4 - 0.6 ms of either), guided step -0.1 ms: not worth a lower arithmetic class by default.
     decode_bwd_feat_mfma = os.environ.get("SSDNERF_DECODE_BWD_FEAT_MFMA", "0") == "1"
+    #: 'eager' (default): a decode whose decoder parameters need a gradient runs grid_sample + nn.Linear under autograd.  'fused' (opt-in: the constructor's
+    #: ``param_grad=``, a config's decoder dict, or SSDNERF_DECODE_PARAM_GRAD=1 for the default of new decoders): the fused decode forward and the parameter
+    #: gradients of csrc/decode_bwd_params.hip (``_PointDecodeParamFn``; fp32 fmas, no atomics, bit-reproducible)
+    param_grad = "fused" if os.environ.get("SSDNERF_DECODE_PARAM_GRAD", "0") == "1" else "eager"
 
     def _point_decode_hip(self, xyzs, dirs, code, density_only, planes=None):
         if planes is None:
