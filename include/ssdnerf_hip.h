@@ -117,7 +117,10 @@ int ssdnerf_sh_encode_backward(const float* grad, const float* inputs, uint32_t 
 #define SSDNERF_MLP_FEATS 18
 #define SSDNERF_MLP_SH 16
 #define SSDNERF_MLP_REC 24 /* per hidden unit: W1[18], b1, w_sigma, Wc[3], pad */
-#define SSDNERF_MLP_PARAM_FLOATS (64 * 24 + 64 * 16 + 64 + 4)
+#define SSDNERF_MLP_OFF_WD (64 * 24)                         /* after the 64 records: Wd[i][0..15] */
+#define SSDNERF_MLP_OFF_BD (SSDNERF_MLP_OFF_WD + 64 * 16)    /* bd[i] */
+#define SSDNERF_MLP_OFF_TAIL (SSDNERF_MLP_OFF_BD + 64)       /* b_sigma, bc[0..2] */
+#define SSDNERF_MLP_PARAM_FLOATS (SSDNERF_MLP_OFF_TAIL + 4)
 
 /* Triplane repack: code (S,3,Cch,Hp,Wp) NCHW (the reference's layout, triplane_decoder.py:125) of dtype
  * code_dtype -> planes (S,3,Hp,Wp,8) channel-last, zero-padded to 8 channels, fp32 (32 B per texel) or

@@ -93,6 +93,11 @@ def lib() -> ctypes.CDLL:
         l.ssdnerf_render_queue_workspace.argtypes = [ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32]
         l.ssdnerf_march_rays_train_batch_workspace.restype = ctypes.c_size_t
         l.ssdnerf_march_rays_train_batch_workspace.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+        l.ssdnerf_triplane_pack.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 4 + [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
+        l.ssdnerf_point_decode.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_uint32, ctypes.c_uint32] + [ctypes.c_void_p] * 3 + [ctypes.c_uint32, ctypes.c_float] + \
+                                          [ctypes.c_void_p] * 3
+        l.ssdnerf_point_decode_backward.argtypes = [ctypes.c_void_p, ctypes.c_int] + [ctypes.c_uint32] * 3 + [ctypes.c_void_p] * 4 + [ctypes.c_uint32, ctypes.c_float] + \
+                                                   [ctypes.c_void_p] * 4 + [ctypes.c_size_t, ctypes.c_void_p]
         l.ssdnerf_point_decode_backward_workspace.restype = ctypes.c_size_t
         l.ssdnerf_point_decode_backward_workspace.argtypes = [ctypes.c_uint32] * 4
         l.ssdnerf_point_decode_backward_layout.restype = None

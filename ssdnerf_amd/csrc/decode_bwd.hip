@@ -26,8 +26,6 @@
 #include "decode_core.h"
 #include "decode_bwd_math.h"
 
-static_assert(SSDB_OFF_WD == MLP_OFF_WD && SSDB_OFF_BD == MLP_OFF_BD && SSDB_OFF_TAIL == MLP_OFF_TAIL, "parameter block layout: decode_core.h and decode_bwd_math.h must agree");
-
 static constexpr unsigned DEC_TPB = 256;
 static constexpr uint32_t DB_TILE = 32;                       // texels per tile edge (k_decode_bwd_bin_owned: four waves, four 16 x 16 quadrants)
 static constexpr uint32_t DB_TILE_FLOATS = DB_TILE * DB_TILE * 6;

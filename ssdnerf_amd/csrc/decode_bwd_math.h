@@ -16,10 +16,11 @@
 // gradient back), ~5.5 kFMA per point, instead of storing 2 x 64 floats per point.
 //
 // The file is plain C on purpose: the device kernel (decode_bwd.hip) and a gcc-built host harness (tests/host/decode_bwd_host.c, which
-// the CPU test checks against PyTorch autograd) compile the SAME arithmetic.  Parameter block layout: decode_core.h.
+// the CPU test checks against PyTorch autograd) compile the SAME arithmetic.  Parameter block layout: decode_core.h; its offsets: ssdnerf_hip.h.
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "../../include/ssdnerf_hip.h"
 
 #ifdef __HIPCC__
 #define SSDB_FN __device__ __forceinline__
@@ -35,9 +36,9 @@
 #define SSDB_UNROLL
 #endif
 
-#define SSDB_OFF_WD (64 * 24)
-#define SSDB_OFF_BD (64 * 24 + 64 * 16)
-#define SSDB_OFF_TAIL (64 * 24 + 64 * 16 + 64)
+#define SSDB_OFF_WD SSDNERF_MLP_OFF_WD
+#define SSDB_OFF_BD SSDNERF_MLP_OFF_BD
+#define SSDB_OFF_TAIL SSDNERF_MLP_OFF_TAIL
 
 SSDB_FN float ssdb_sigmoid(float u) { return SSDB_RCP(1.0f + SSDB_EXP2(u * -1.4426950408889634f)); }
 
@@ -79,9 +80,10 @@ SSDB_FN void ssdb_gather18(const float* planes, uint32_t Hp, uint32_t Wp, float 
     }
 }
 
-// dL/df[18] of one point.  ``color`` = 0: density head only (g_rgb, sh ignored).
-SSDB_FN void ssdb_mlp_backward(const float* __restrict__ P, const float f[18], const float sh[16], float sat, float g_sigma, const float g_rgb[3],
-                               int color, float gf[18]) {
+// the two heads' pre-activations of one point, then dL/dsa and dL/dz[3].  ``color`` = 0: density head only (g_rgb, sh ignored; dz = 0).  The parameter gradient
+// (decode_bwd_params_math.h) starts from the same routine, in its colour form
+SSDB_FN void ssdb_heads(const float* __restrict__ P, const float f[18], const float sh[16], float sat, float g_sigma, const float g_rgb[3], int color, float* dsa,
+                        float dz[3]) {
     float sa = P[SSDB_OFF_TAIL + 0];
     float z0 = P[SSDB_OFF_TAIL + 1], z1 = P[SSDB_OFF_TAIL + 2], z2 = P[SSDB_OFF_TAIL + 3];
     for (int i = 0; i < 64; ++i) {
@@ -102,15 +104,22 @@ SSDB_FN void ssdb_mlp_backward(const float* __restrict__ P, const float f[18], c
         }
     }
     const float e = SSDB_EXP2(sa * 1.4426950408889634f);
-    const float dsa = g_sigma * fminf(1e6f, fmaxf(e, 1e-6f));
-    float dz0 = 0.0f, dz1 = 0.0f, dz2 = 0.0f;
+    *dsa = g_sigma * fminf(1e6f, fmaxf(e, 1e-6f));
+    dz[0] = dz[1] = dz[2] = 0.0f;
     if (color) {
         const float k = fmaf(sat, 2.0f, 1.0f);
         const float s0 = ssdb_sigmoid(z0), s1 = ssdb_sigmoid(z1), s2 = ssdb_sigmoid(z2);
-        dz0 = g_rgb[0] * k * (s0 * (1.0f - s0));
-        dz1 = g_rgb[1] * k * (s1 * (1.0f - s1));
-        dz2 = g_rgb[2] * k * (s2 * (1.0f - s2));
+        dz[0] = g_rgb[0] * k * (s0 * (1.0f - s0));
+        dz[1] = g_rgb[1] * k * (s1 * (1.0f - s1));
+        dz[2] = g_rgb[2] * k * (s2 * (1.0f - s2));
     }
+}
+
+// dL/df[18] of one point.  ``color`` = 0: density head only (g_rgb, sh ignored).
+SSDB_FN void ssdb_mlp_backward(const float* __restrict__ P, const float f[18], const float sh[16], float sat, float g_sigma, const float g_rgb[3],
+                               int color, float gf[18]) {
+    float dsa, dz[3];
+    ssdb_heads(P, f, sh, sat, g_sigma, g_rgb, color, &dsa, dz);
     SSDB_UNROLL
     for (int k = 0; k < 18; ++k) gf[k] = 0.0f;
     for (int i = 0; i < 64; ++i) {
@@ -126,7 +135,7 @@ SSDB_FN void ssdb_mlp_backward(const float* __restrict__ P, const float f[18], c
             SSDB_UNROLL
             for (int m = 0; m < 16; ++m) d = fmaf(wd[m], sh[m], d);
             const float u = h + d, su = ssdb_sigmoid(u);
-            const float dc = fmaf(dz2, rec[22], fmaf(dz1, rec[21], dz0 * rec[20]));
+            const float dc = fmaf(dz[2], rec[22], fmaf(dz[1], rec[21], dz[0] * rec[20]));
             dh = fmaf(dc, su * fmaf(u, 1.0f - su, 1.0f), dh);
         }
         SSDB_UNROLL

@@ -3,7 +3,7 @@
 //
 //   k_decode_bwd_params      persistent blocks of four waves in a grid-stride loop over 256-sample groups; wave w of a block takes samples [64 w, 64 w + 64) of a group.
 //                            STAGE 1, lane = sample: the samples WITH an upstream gradient (not the alignment padding, not the samples behind the T_thresh cut)
-//                            re-gather their 18 features, evaluate the SH basis and run ssdp_heads (the hidden units once, to dL/dsa and dL/dz); they leave
+//                            re-gather their 18 features, evaluate the SH basis and run ssdb_heads (the hidden units once, to dL/dsa and dL/dz); they leave
 //                            {f[18], SH[16], dsa, dz[3]} in the wave's own LDS rows, compacted in sample order.
 //                            STAGE 2, the wave turns round, lane = hidden unit i: the lane holds its unit's 40 weights in registers and walks the wave's rows in order
 //                            with broadcast LDS reads (every lane reads the same address); per sample it recomputes h_i and u_i (34 fmas, two sigmoids) and adds the
@@ -17,9 +17,6 @@
 // formed in a fixed order: two calls on the same inputs with the same block count give the same bits.  Plain fp32 fmas: the arithmetic class of k_decode_bwd_feat.
 #include "decode_core.h"
 #include "decode_bwd_params_math.h"
-
-static_assert(SSDB_OFF_WD == MLP_OFF_WD && SSDB_OFF_BD == MLP_OFF_BD && SSDB_OFF_TAIL == MLP_OFF_TAIL && SSDP_PARAM_FLOATS == SSDNERF_MLP_PARAM_FLOATS,
-              "parameter block layout: decode_core.h, decode_bwd_math.h and ssdnerf_hip.h must agree");
 
 static constexpr unsigned DBP_TPB = 256;
 static constexpr unsigned DBP_WAVES = DBP_TPB / 64;
@@ -101,7 +98,7 @@ __global__ void __launch_bounds__(DBP_TPB, 2) k_decode_bwd_params(const PT* __re
             float f[18], sh[16], dsa, dz[3];
             ssd_gather18<PT>(planes + scene * plane_stride, g, xyzs[3ull * i], xyzs[3ull * i + 1], xyzs[3ull * i + 2], f);
             shb::eval<4, false>(dirs[3ull * i], dirs[3ull * i + 1], dirs[3ull * i + 2], sh, nullptr, nullptr, nullptr);
-            ssdp_heads(P, f, sh, sat, gs, gc, &dsa, dz);
+            ssdb_heads(P, f, sh, sat, gs, gc, 1, &dsa, dz);
             const uint32_t slot = __builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));     // rank among the wave's samples with a gradient
             float4* dst = reinterpret_cast<float4*>(my_rows + slot * DBP_ROW);
             dst[0] = make_float4(f[0], f[1], f[2], f[3]);

@@ -10,51 +10,23 @@
 //   dws_i  += dsa silu(h_i)               dbs   += dsa
 //   dWc_ji += dz_j silu(u_i)              dbc_j += dz_j
 //
-// with dsa and dz_j formed exactly as ssdb_mlp_backward forms them (ssdp_heads below is its first half) and a_i + e_i formed as its dh_i: fma(dc_i, silu'(u_i), a_i).
+// with dsa and dz_j from ssdb_heads (decode_bwd_math.h, colour form: the routine ssdb_mlp_backward starts from) and a_i + e_i formed as its dh_i: fma(dc_i, silu'(u_i), a_i).
 // No gradient flows to positions or directions.
 //
-// The arithmetic is split where the kernel (decode_bwd_params.hip) turns round: ssdp_heads runs with one SAMPLE per lane, ssdp_unit_add with one HIDDEN UNIT per lane,
-// which recomputes its own h_i and u_i from the sample's features (the same fma chains, so the same bits as in ssdp_heads) and adds the sample's terms into the
+// The arithmetic is split where the kernel (decode_bwd_params.hip) turns round: ssdb_heads runs with one SAMPLE per lane, ssdp_unit_add with one HIDDEN UNIT per lane,
+// which recomputes its own h_i and u_i from the sample's features (the same fma chains, so the same bits as in ssdb_heads) and adds the sample's terms into the
 // SSDP_ACC accumulators of its row.  Every accumulation is a plain fp32 fma or add: the sum of an element is formed in the order in which the samples are handed in.
 // Plain C like decode_bwd_math.h: the kernel and the host harness (tests/host/decode_bwd_params_host.c) compile the SAME arithmetic.
 #pragma once
 #include "decode_bwd_math.h"
 
-#define SSDP_PARAM_FLOATS (64 * 24 + 64 * 16 + 64 + 4)
+#define SSDP_PARAM_FLOATS SSDNERF_MLP_PARAM_FLOATS
 // accumulators of hidden unit i, in the order of its record: [0, 18) dW1_i, 18 db1_i, 19 dws_i, 20 .. 22 dWc_{0..2},i; then [23, 39) dWd_i, 39 dbd_i; then the four
 // sums that do not depend on i (every unit forms them, identically; unit 0's are stored): 40 dbs, 41 .. 43 dbc
 #define SSDP_ACC 44
 #define SSDP_ACC_WD 23
 #define SSDP_ACC_BD 39
 #define SSDP_ACC_TAIL 40
-
-// the first half of ssdb_mlp_backward (colour form): the two heads' pre-activations, then dL/dsa and dL/dz
-SSDB_FN void ssdp_heads(const float* __restrict__ P, const float f[18], const float sh[16], float sat, float g_sigma, const float g_rgb[3], float* dsa, float dz[3]) {
-    float sa = P[SSDB_OFF_TAIL + 0];
-    float z0 = P[SSDB_OFF_TAIL + 1], z1 = P[SSDB_OFF_TAIL + 2], z2 = P[SSDB_OFF_TAIL + 3];
-    for (int i = 0; i < 64; ++i) {
-        const float* __restrict__ rec = P + i * 24;
-        float h = rec[18];
-        SSDB_UNROLL
-        for (int k = 0; k < 18; ++k) h = fmaf(rec[k], f[k], h);
-        sa = fmaf(rec[19], h * ssdb_sigmoid(h), sa);
-        float d = P[SSDB_OFF_BD + i];
-        const float* __restrict__ wd = P + SSDB_OFF_WD + i * 16;
-        SSDB_UNROLL
-        for (int m = 0; m < 16; ++m) d = fmaf(wd[m], sh[m], d);
-        const float u = h + d, c = u * ssdb_sigmoid(u);
-        z0 = fmaf(rec[20], c, z0);
-        z1 = fmaf(rec[21], c, z1);
-        z2 = fmaf(rec[22], c, z2);
-    }
-    const float e = SSDB_EXP2(sa * 1.4426950408889634f);
-    *dsa = g_sigma * fminf(1e6f, fmaxf(e, 1e-6f));
-    const float k = fmaf(sat, 2.0f, 1.0f);
-    const float s0 = ssdb_sigmoid(z0), s1 = ssdb_sigmoid(z1), s2 = ssdb_sigmoid(z2);
-    dz[0] = g_rgb[0] * k * (s0 * (1.0f - s0));
-    dz[1] = g_rgb[1] * k * (s1 * (1.0f - s1));
-    dz[2] = g_rgb[2] * k * (s2 * (1.0f - s2));
-}
 
 // one sample's terms of hidden unit i, added to the unit's accumulators.  rec = the unit's record (W1_i[18], b1_i, w_s,i, Wc_{0..2},i), wd = Wd_i[16], bd = bd_i
 SSDB_FN void ssdp_unit_add(const float rec[23], const float wd[16], float bd, const float f[18], const float sh[16], float dsa, const float dz[3],

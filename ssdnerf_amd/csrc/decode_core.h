@@ -22,10 +22,9 @@
 #include "common.h"
 #include "sh_basis.h"
 
-
-#define MLP_OFF_WD (64 * 24)
-#define MLP_OFF_BD (64 * 24 + 64 * 16)
-#define MLP_OFF_TAIL (64 * 24 + 64 * 16 + 64)
+#define MLP_OFF_WD SSDNERF_MLP_OFF_WD
+#define MLP_OFF_BD SSDNERF_MLP_OFF_BD
+#define MLP_OFF_TAIL SSDNERF_MLP_OFF_TAIL
 
 template <typename PT> struct Texel;
 template <> struct Texel<float> {

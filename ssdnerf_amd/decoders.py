@@ -9,8 +9,8 @@ fast path behind them:
 * ``point_decode`` / ``point_density_decode`` on packed sample lists -> one fused HIP decode per scene; when only the
   scene code needs a gradient (guidance, fine-tuning) the backward is fused too (``_PointDecodeFn``: re-gather +
   recomputed MLP + atomic scatter); an eager PyTorch-ROCm path remains for decoder-parameter gradients (autograd;
-  also the "reference-shaped eager" baseline B1), unless ``param_grad='fused'`` opts into ``_PointDecodeParamFn``: the fused
-  forward and the parameter gradients of csrc/decode_bwd_params.hip.
+  also the "reference-shaped eager" baseline B1), unless ``param_grad='fused'`` opts in: the same ``_PointDecodeFn``, whose
+  backward then also runs the parameter gradients of csrc/decode_bwd_params.hip.
 * train branch -> per-scene ``march_rays_train`` (deterministic prefix-sum packing) + decode +
   ``batch_composite_rays_train`` (HIP forward/backward kernels).
 
@@ -19,6 +19,7 @@ parity tests and as the exact fallback when the fused kernel reports a ray at th
 """
 from __future__ import annotations
 
+import itertools
 import os
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -33,7 +34,12 @@ from .raymarching import (batch_composite_rays_train, batch_near_far_from_aabb, 
 from .registry import MODULES, build_module
 from .shencoder import SHEncoder
 
-MLP_PARAM_FLOATS = 64 * 24 + 64 * 16 + 64 + 4
+MLP_OFF_WD = 64 * 24                      # the packed parameter block: SSDNERF_MLP_OFF_* / SSDNERF_MLP_PARAM_FLOATS of include/ssdnerf_hip.h (layout: csrc/decode_core.h)
+MLP_OFF_BD = MLP_OFF_WD + 64 * 16
+MLP_OFF_TAIL = MLP_OFF_BD + 64
+MLP_PARAM_FLOATS = MLP_OFF_TAIL + 4
+#: the eight tensors of the block in pack order: W1, b1, ws, bs, Wd, bd, Wc, bc
+MLP_PARAM_KEYS = tuple(f"{net}.0.{kind}" for net in ("base_net", "density_net", "dir_net", "color_net") for kind in ("weight", "bias"))
 
 
 def _per_scene_floats(dt_gamma, num_scenes):
@@ -65,70 +71,27 @@ def pack_triplanes(code: torch.Tensor, dtype: torch.dtype = torch.float32) -> to
 
 def pack_mlp_params(sd: Dict[str, torch.Tensor], device) -> torch.Tensor:
     """Reference state-dict tensors -> the packed parameter block of the fused kernels (layout: csrc/decode_core.h)."""
-    w1, b1 = sd["base_net.0.weight"].float(), sd["base_net.0.bias"].float()          # (64,18), (64)
-    ws, bs = sd["density_net.0.weight"].float(), sd["density_net.0.bias"].float()    # (1,64), (1)
-    wd, bd = sd["dir_net.0.weight"].float(), sd["dir_net.0.bias"].float()            # (64,16), (64)
-    wc, bc = sd["color_net.0.weight"].float(), sd["color_net.0.bias"].float()        # (3,64), (3)
-    rec = torch.zeros(64, 24, dtype=torch.float32, device=w1.device)
-    rec[:, :18] = w1
-    rec[:, 18] = b1
-    rec[:, 19] = ws[0]
-    rec[:, 20:23] = wc.t()
-    out = torch.cat([rec.reshape(-1), wd.reshape(-1), bd.reshape(-1), bs.reshape(-1), bc.reshape(-1)])
-    assert out.numel() == MLP_PARAM_FLOATS
+    out = torch.zeros(MLP_PARAM_FLOATS, dtype=torch.float32, device=sd["base_net.0.weight"].device)      # (the records' unused column stays 0)
+    for dst, key in zip(unpack_mlp_grads(out), MLP_PARAM_KEYS):
+        dst.copy_(sd[key])
     return out.to(device).contiguous()
 
 
+def unpack_mlp_grads(gp: torch.Tensor):
+    """The inverse of ``pack_mlp_params``: a packed block (the parameter gradient of csrc/decode_bwd_params.hip) -> views of it with the shapes of the eight tensors,
+    in the order of ``MLP_PARAM_KEYS``.  Wc sits transposed in the records."""
+    rec = gp[:MLP_OFF_WD].view(64, 24)
+    return (rec[:, :18], rec[:, 18], rec[:, 19].unsqueeze(0), gp[MLP_OFF_TAIL:MLP_OFF_TAIL + 1],          # W1 (64,18), b1 (64), ws (1,64), bs (1)
+            gp[MLP_OFF_WD:MLP_OFF_BD].view(64, 16), gp[MLP_OFF_BD:MLP_OFF_TAIL], rec[:, 20:23].t(), gp[MLP_OFF_TAIL + 1:])     # Wd (64,16), bd (64), Wc (3,64), bc (3)
+
+
 class _PointDecodeFn(torch.autograd.Function):
-    """Fused point decode, differentiable w.r.t. the scene code with the decoder frozen: forward = ``ssdnerf_point_decode`` per scene,
-    backward = ONE ``ssdnerf_point_decode_backward`` for the whole batch (re-gather, recompute the hidden units, binned reduction of the
-    corner contributions in LDS, gradient written in the code's NCHW layout) instead of autograd through grid_sample + 4 nn.Linear
-    (~20 eager kernels each way and ``grid_sampler_2d_backward``, which alone was 30 % of a guided DDIM step).  Sample positions and
-    view directions are data: no gradient flows to them."""
-
-    @staticmethod
-    def forward(ctx, code, decoder, xyzs, dirs):
-        planes = pack_triplanes(code.detach(), decoder.plane_dtype)
-        xyzs = [x.detach().reshape(-1, 3).float().contiguous() for x in xyzs]
-        dirs = [d.detach().reshape(-1, 3).float().contiguous() for d in dirs]
-        sigmas, rgbs, num_points = decoder._point_decode_hip(xyzs, dirs, code, False, planes=planes)
-        ctx.decoder, ctx.planes, ctx.xyzs, ctx.dirs, ctx.num_points = decoder, planes, xyzs, dirs, num_points
-        ctx.code_meta = (code.shape, code.dtype)
-        return sigmas, rgbs
-
-    @staticmethod
-    def backward(ctx, g_sigmas, g_rgbs):
-        decoder, planes = ctx.decoder, ctx.planes
-        shape, dtype = ctx.code_meta
-        s_, _, c, hp, wp = shape
-        assert c == 6, "the fused decode gradient is written for 6-channel planes (18 features)"
-        total = sum(ctx.num_points)
-        dev = planes.device
-        g_sigmas = torch.zeros(total, dtype=torch.float32, device=dev) if g_sigmas is None else g_sigmas.float().contiguous()
-        g_rgbs = torch.zeros(total, 3, dtype=torch.float32, device=dev) if g_rgbs is None else g_rgbs.float().contiguous()
-        xyzs = ctx.xyzs[0] if s_ == 1 else torch.cat(ctx.xyzs, dim=0)
-        dirs = ctx.dirs[0] if s_ == 1 else torch.cat(ctx.dirs, dim=0)
-        bounds = [0]
-        for n in ctx.num_points:
-            bounds.append(bounds[-1] + n)
-        offsets = torch.tensor(bounds, dtype=torch.int32, device=dev)          # (a blocking copy: the host list dies with this frame)
-        grad_code = torch.empty(s_, 3, 6, hp, wp, dtype=torch.float32, device=dev)
-        ws_bytes = int(C.lib().ssdnerf_point_decode_backward_workspace(C.u32(s_), C.u32(total), C.u32(hp), C.u32(wp)))
-        ws = decoder._workspace(max(ws_bytes, 1), dev, "decode_bwd")                       # the decoder's cached scratch (grown on demand), not a fresh tensor per backward
-        C.check(C.lib().ssdnerf_point_decode_backward(
-            C.ptr(planes), C.dtype_code(planes) | (0x100 if getattr(decoder, "decode_bwd_feat_mfma", False) else 0), C.u32(s_), C.u32(hp), C.u32(wp),
-            C.ptr(decoder.packed_params()), C.ptr(xyzs), C.ptr(dirs),
-            C.ptr(offsets), C.u32(total), C.f32(decoder.sigmoid_saturation), C.ptr(g_sigmas), C.ptr(g_rgbs), C.ptr(grad_code), C.ptr(ws),
-            C.ctypes.c_size_t(ws_bytes), C.stream()), "point_decode_backward")
-        return grad_code.to(dtype), None, None, None
-
-
-class _PointDecodeParamFn(torch.autograd.Function):
-    """Fused point decode, differentiable w.r.t. the scene code AND the decoder's eight parameter tensors (``param_grad='fused'``: the closing joint iteration of a
-    training step).  forward = ``_PointDecodeFn``'s, on ``packed_params()``; backward = ONE ``ssdnerf_point_decode_backward_params`` for the whole batch (re-gather,
-    recomputed hidden units, the sum over the samples in per-lane registers, no atomics, fixed order: bit-reproducible), whose packed gradient is sliced back into the
-    eight tensors, and -- only when the code needs a gradient -- the unchanged ``ssdnerf_point_decode_backward``.  The parameter tensors are inputs so that autograd
-    routes their gradients; the kernels read the packed block."""
+    """Fused point decode, differentiable w.r.t. the scene code and the decoder's eight parameter tensors (pack order; inputs so that autograd routes their gradients:
+    the kernels read the packed block the forward read, ``ctx.packed``).  forward = ``ssdnerf_point_decode`` per scene.  backward, for the whole batch and only where an
+    input needs it: ONE ``ssdnerf_point_decode_backward_params`` (the sum over the samples in per-lane registers, no atomics, fixed order: bit-reproducible) and ONE
+    ``ssdnerf_point_decode_backward`` (binned reduction of the corner contributions in LDS, gradient in the code's NCHW layout; a frozen decoder launches this one only),
+    both on re-gathered features and recomputed hidden units, instead of autograd through grid_sample + 4 nn.Linear (~20 eager kernels each way and
+    ``grid_sampler_2d_backward``, alone 30 % of a guided DDIM step).  Sample positions and view directions are data: no gradient flows to them."""
 
     @staticmethod
     def forward(ctx, code, w1, b1, ws, bs, wd, bd, wc, bc, decoder, xyzs, dirs):
@@ -137,50 +100,40 @@ class _PointDecodeParamFn(torch.autograd.Function):
         dirs = [d.detach().reshape(-1, 3).float().contiguous() for d in dirs]
         sigmas, rgbs, num_points = decoder._point_decode_hip(xyzs, dirs, code, False, planes=planes)
         ctx.decoder, ctx.planes, ctx.xyzs, ctx.dirs, ctx.num_points = decoder, planes, xyzs, dirs, num_points
-        ctx.packed = decoder.packed_params()                                   # the block the forward read (an optimizer step before backward re-packs into a new tensor)
-        ctx.code_meta = (code.shape, code.dtype)
-        ctx.param_dtypes = tuple(p.dtype for p in (w1, b1, ws, bs, wd, bd, wc, bc))
+        ctx.packed = decoder.packed_params()                                   # the block the forward read (a change of the weights before backward re-packs into a new tensor)
+        ctx.code_meta, ctx.param_dtypes = (code.shape, code.dtype), tuple(p.dtype for p in (w1, b1, ws, bs, wd, bd, wc, bc))
         return sigmas, rgbs
 
     @staticmethod
     def backward(ctx, g_sigmas, g_rgbs):
-        decoder, planes, packed = ctx.decoder, ctx.planes, ctx.packed
-        shape, code_dtype = ctx.code_meta
-        s_, _, c, hp, wp = shape
+        decoder, planes = ctx.decoder, ctx.planes
+        (s_, _, c, hp, wp), code_dtype = ctx.code_meta
         assert c == 6, "the fused decode gradient is written for 6-channel planes (18 features)"
-        total = sum(ctx.num_points)
-        dev = planes.device
+        total, dev = sum(ctx.num_points), planes.device
         g_sigmas = torch.zeros(total, dtype=torch.float32, device=dev) if g_sigmas is None else g_sigmas.float().contiguous()
         g_rgbs = torch.zeros(total, 3, dtype=torch.float32, device=dev) if g_rgbs is None else g_rgbs.float().contiguous()
         xyzs = ctx.xyzs[0] if s_ == 1 else torch.cat(ctx.xyzs, dim=0)
         dirs = ctx.dirs[0] if s_ == 1 else torch.cat(ctx.dirs, dim=0)
-        bounds = [0]
-        for n in ctx.num_points:
-            bounds.append(bounds[-1] + n)
-        offsets = torch.tensor(bounds, dtype=torch.int32, device=dev)          # (a blocking copy: the host list dies with this frame)
+        offsets = torch.tensor([0, *itertools.accumulate(ctx.num_points)], dtype=torch.int32, device=dev)          # (a blocking copy: the host list dies with this frame)
         lib = C.lib()
+        batch = (C.u32(s_), C.u32(hp), C.u32(wp), C.ptr(ctx.packed), C.ptr(xyzs), C.ptr(dirs), C.ptr(offsets), C.u32(total), C.f32(decoder.sigmoid_saturation),
+                 C.ptr(g_sigmas), C.ptr(g_rgbs))                                # what the two entry points share, between planes_dtype and the result
         grads = [None] * 9
         if any(ctx.needs_input_grad[1:9]):
             gp = torch.empty(MLP_PARAM_FLOATS, dtype=torch.float32, device=dev)
             ws_bytes = int(lib.ssdnerf_point_decode_backward_params_workspace(C.u32(s_), C.u32(total), C.u32(0)))
-            ws = decoder._workspace(max(ws_bytes, 1), dev, "decode_bwd_params")
-            C.check(lib.ssdnerf_point_decode_backward_params(
-                C.ptr(planes), C.dtype_code(planes), C.u32(s_), C.u32(hp), C.u32(wp), C.ptr(packed), C.ptr(xyzs), C.ptr(dirs), C.ptr(offsets), C.u32(total),
-                C.f32(decoder.sigmoid_saturation), C.ptr(g_sigmas), C.ptr(g_rgbs), C.ptr(gp), C.u32(0), C.ptr(ws), C.ctypes.c_size_t(ws_bytes), C.stream()),
-                "point_decode_backward_params")
-            rec = gp[:64 * 24].view(64, 24)                                    # the packed layout of csrc/decode_core.h; Wc sits transposed in the records
-            sliced = (rec[:, :18], rec[:, 18], rec[:, 19].unsqueeze(0), gp[2624:2625], gp[1536:2560].view(64, 16), gp[2560:2624], rec[:, 20:23].t(), gp[2625:2628])
-            for i, (g, dt) in enumerate(zip(sliced, ctx.param_dtypes)):
+            ws = decoder._workspace(max(ws_bytes, 1), dev, "decode_bwd_params")            # the decoder's cached scratch (grown on demand), not a fresh tensor per backward
+            C.check(lib.ssdnerf_point_decode_backward_params(C.ptr(planes), C.dtype_code(planes), *batch, C.ptr(gp), C.u32(0), C.ptr(ws), C.ctypes.c_size_t(ws_bytes),
+                                                             C.stream()), "point_decode_backward_params")
+            for i, (g, dt) in enumerate(zip(unpack_mlp_grads(gp), ctx.param_dtypes)):
                 if ctx.needs_input_grad[1 + i]:
                     grads[1 + i] = g.to(dt).contiguous()
         if ctx.needs_input_grad[0]:
             grad_code = torch.empty(s_, 3, 6, hp, wp, dtype=torch.float32, device=dev)
             ws_bytes = int(lib.ssdnerf_point_decode_backward_workspace(C.u32(s_), C.u32(total), C.u32(hp), C.u32(wp)))
             ws = decoder._workspace(max(ws_bytes, 1), dev, "decode_bwd")
-            C.check(lib.ssdnerf_point_decode_backward(
-                C.ptr(planes), C.dtype_code(planes) | (0x100 if getattr(decoder, "decode_bwd_feat_mfma", False) else 0), C.u32(s_), C.u32(hp), C.u32(wp),
-                C.ptr(packed), C.ptr(xyzs), C.ptr(dirs), C.ptr(offsets), C.u32(total), C.f32(decoder.sigmoid_saturation), C.ptr(g_sigmas), C.ptr(g_rgbs),
-                C.ptr(grad_code), C.ptr(ws), C.ctypes.c_size_t(ws_bytes), C.stream()), "point_decode_backward")
+            C.check(lib.ssdnerf_point_decode_backward(C.ptr(planes), C.dtype_code(planes) | (0x100 if getattr(decoder, "decode_bwd_feat_mfma", False) else 0), *batch,
+                                                      C.ptr(grad_code), C.ptr(ws), C.ctypes.c_size_t(ws_bytes), C.stream()), "point_decode_backward")
             grads[0] = grad_code.to(code_dtype)
         return (*grads, None, None, None)
 
@@ -423,17 +376,18 @@ class TriPlaneDecoder(VolumeRenderer):
             ok = ok and code.dim() == 5 and code.size(1) == 3 and code.size(2) == 6 and code.is_cuda
         return ok
 
-    def packed_params(self) -> torch.Tensor:
+    def _mlp_parameters(self) -> List[torch.Tensor]:
+        """the eight parameter tensors in pack order (``MLP_PARAM_KEYS``)"""
         cached = self.__dict__.get("_packed_ps")                         # (the four Linear modules, looked up once: Sequential.__getitem__ is slow)
         if cached is None:
             cached = self.__dict__["_packed_ps"] = (self.base_net[0], self.density_net[0], self.dir_net[0], self.color_net[0])
-        ps = [p for m in cached for p in (m._parameters["weight"], m._parameters["bias"])]
+        return [p for m in cached for p in (m._parameters["weight"], m._parameters["bias"])]
+
+    def packed_params(self) -> torch.Tensor:
+        ps = self._mlp_parameters()
         key = tuple((p.data_ptr(), p._version, p.device.index, p.dtype) for p in ps)     # (writes through p.data bypass this: call invalidate_packed())
         if self._packed is None or key != self._packed_key:
-            sd = {"base_net.0.weight": ps[0].detach(), "base_net.0.bias": ps[1].detach(), "density_net.0.weight": ps[2].detach(),
-                  "density_net.0.bias": ps[3].detach(), "dir_net.0.weight": ps[4].detach(), "dir_net.0.bias": ps[5].detach(),
-                  "color_net.0.weight": ps[6].detach(), "color_net.0.bias": ps[7].detach()}
-            self._packed = pack_mlp_params(sd, ps[0].device)
+            self._packed = pack_mlp_params({k: p.detach() for k, p in zip(MLP_PARAM_KEYS, ps)}, ps[0].device)
             self._packed_key = key
         return self._packed
 
@@ -482,20 +436,14 @@ class TriPlaneDecoder(VolumeRenderer):
             return self.point_decode_eager(xyzs, dirs, code, density_only)
         if not need_grad and self.fused_supported(code):
             return self._point_decode_hip(xyzs, dirs, code, density_only)
-        if (self.fused_code_grad and not params_need_grad and not density_only and dirs is not None and code.is_cuda
+        if ((self.param_grad == "fused" if params_need_grad else self.fused_code_grad) and not density_only and dirs is not None and code.is_cuda
                 and self.fused_supported(code)):
-            # gradient w.r.t. the code only (guidance, val_optim / inverse_code with the decoder frozen): fused forward AND backward
+            # fused forward AND backward: the code's gradient with the decoder frozen (guidance, val_optim / inverse_code), or -- a trainable decoder, opted in: the
+            # closing joint iteration of a training step -- the parameters' and, when it needs one, the code's.  Dropout in training, scene_base, other layer shapes
+            # and CPU tensors are not ``fused_supported``: eager, below
             if isinstance(xyzs, torch.Tensor):
                 xyzs, dirs = list(xyzs), list(dirs)
-            sigmas, rgbs = _PointDecodeFn.apply(code, self, xyzs, dirs)
-            return sigmas, rgbs, [int(x.size(-2)) for x in xyzs]
-        if self.param_grad == "fused" and params_need_grad and not density_only and dirs is not None and self.fused_supported(code):
-            # a trainable decoder (the closing joint iteration of a training step), opted in: fused forward, parameter gradients -- and the code's, when it
-            # needs one -- from the HIP kernels.  Dropout in training, scene_base, other layer shapes and CPU tensors are not ``fused_supported``: eager, below
-            if isinstance(xyzs, torch.Tensor):
-                xyzs, dirs = list(xyzs), list(dirs)
-            ps = [p for m in (self.base_net[0], self.density_net[0], self.dir_net[0], self.color_net[0]) for p in (m.weight, m.bias)]
-            sigmas, rgbs = _PointDecodeParamFn.apply(code, *ps, self, xyzs, dirs)
+            sigmas, rgbs = _PointDecodeFn.apply(code, *self._mlp_parameters(), self, xyzs, dirs)
             return sigmas, rgbs, [int(x.size(-2)) for x in xyzs]
         return self.point_decode_eager(xyzs, dirs, code, density_only)
 
@@ -510,7 +458,7 @@ class TriPlaneDecoder(VolumeRenderer):
     decode_bwd_feat_mfma = os.environ.get("SSDNERF_DECODE_BWD_FEAT_MFMA", "0") == "1"
     #: 'eager' (default): a decode whose decoder parameters need a gradient runs grid_sample + nn.Linear under autograd.  'fused' (opt-in: the constructor's
     #: ``param_grad=``, a config's decoder dict, or SSDNERF_DECODE_PARAM_GRAD=1 for the default of new decoders): the fused decode forward and the parameter
-    #: gradients of csrc/decode_bwd_params.hip (``_PointDecodeParamFn``; fp32 fmas, no atomics, bit-reproducible)
+    #: gradients of csrc/decode_bwd_params.hip (``_PointDecodeFn``; fp32 fmas, no atomics, bit-reproducible)
     param_grad = "fused" if os.environ.get("SSDNERF_DECODE_PARAM_GRAD", "0") == "1" else "eager"
 
     def _point_decode_hip(self, xyzs, dirs, code, density_only, planes=None):

@@ -17,7 +17,7 @@ void decode_bwd_params_points(const float* planes, uint32_t Hp, uint32_t Wp, con
         float f[18], dsa, dz[3];
         const float* sh = shs + 16 * (uint64_t)s;
         ssdb_gather18(planes, Hp, Wp, xyzs[3 * s], xyzs[3 * s + 1], xyzs[3 * s + 2], f);
-        ssdp_heads(P, f, sh, sat, gs, gc, &dsa, dz);
+        ssdb_heads(P, f, sh, sat, gs, gc, 1, &dsa, dz);
         for (int i = 0; i < 64; ++i) ssdp_unit_add(P + i * 24, P + SSDB_OFF_WD + i * 16, P[SSDB_OFF_BD + i], f, sh, dsa, dz, acc[i]);
     }
     for (int i = 0; i < 64; ++i) ssdp_store_row(acc[i], i, scene);

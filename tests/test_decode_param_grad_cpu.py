@@ -181,6 +181,35 @@ def test_param_grad_switch_of_the_decoder():
     assert dec.base_net[0].weight.grad is not None and code.grad is not None
 
 
+def test_unpack_mlp_grads_inverts_pack_mlp_params():
+    """the eight tensors of a random state dict come back bit for bit and in their shapes: Wc transposed back, the biases (1,) and (3,)"""
+    from ssdnerf_amd.decoders import MLP_PARAM_FLOATS, MLP_PARAM_KEYS, pack_mlp_params, unpack_mlp_grads
+    shapes = [(64, 18), (64,), (1, 64), (1,), (64, 16), (64,), (3, 64), (3,)]
+    gen = torch.Generator().manual_seed(7)
+    sd = {k: torch.randn(shp, generator=gen) for k, shp in zip(MLP_PARAM_KEYS, shapes)}
+    assert list(MLP_PARAM_KEYS) == list(PG.NAMES)
+    packed = pack_mlp_params(sd, "cpu")
+    assert packed.shape == (MLP_PARAM_FLOATS,) and not packed[:1536].view(64, 24)[:, 23].any()
+    back = unpack_mlp_grads(packed)
+    assert len(back) == 8
+    for k, shp, got in zip(MLP_PARAM_KEYS, shapes, back):
+        assert tuple(got.shape) == shp and torch.equal(got.contiguous().view(torch.int32), sd[k].view(torch.int32)), k
+    for k, got in PG.unpack(packed.numpy()).items():                         # ... and the reference's own unpacking reads the same block the same way
+        assert np.array_equal(got, sd[k].numpy()), k
+
+
+def test_python_layout_offsets_are_the_headers():
+    from ssdnerf_amd import decoders as D
+    tmp = tempfile.mkdtemp(prefix="mlp_layout")
+    src, exe = os.path.join(tmp, "layout.c"), os.path.join(tmp, "layout")
+    with open(src, "w") as f:
+        f.write('#include <stdio.h>\n#include "ssdnerf_hip.h"\n'
+                'int main(void) { printf("%d %d %d %d\\n", SSDNERF_MLP_OFF_WD, SSDNERF_MLP_OFF_BD, SSDNERF_MLP_OFF_TAIL, SSDNERF_MLP_PARAM_FLOATS); return 0; }\n')
+    subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout
+    assert [int(v) for v in out.split()] == [D.MLP_OFF_WD, D.MLP_OFF_BD, D.MLP_OFF_TAIL, D.MLP_PARAM_FLOATS] == [1536, 2560, 2624, 2628]
+
+
 def test_environment_sets_the_default_of_new_decoders():
     import sys
     prog = ("from ssdnerf_amd.decoders import TriPlaneDecoder as T; "

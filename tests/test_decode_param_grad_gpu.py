@@ -4,7 +4,8 @@ of tests/_decode_param_grad_ref.py, on the seeded families tests/test_decode_par
     bound, unreached elements (the padding column) exactly 0; two calls give the same bits; no samples, or no upstream gradient, give zeros; argument errors return
     their codes and write nothing;
   * through Python: ``point_decode`` leaves in the eight ``.grad`` tensors what the reference says (unpacking, the transposed Wc), ``code.grad`` meets the end-to-end
-    bounds of tests/_decode_grad_ref.py, a frozen parameter gets no gradient, and without gradients or with ``param_grad='eager'`` the new entry point is not called;
+    bounds of tests/_decode_grad_ref.py, a frozen parameter gets no gradient, without gradients or with ``param_grad='eager'`` the new entry point is not called, and
+    a frozen decoder whose weights change in place before the backward still gets the gradient of the network its forward evaluated;
   * one ``MultiSceneNeRF.train_step`` with ``param_grad='fused'`` never enters the eager decode and leaves the gradients of the eager-mode run of the same seeded step
     (cosine >= 0.999: a check of the WIRING against gross errors, not a precision claim -- precision is the bound tests' job)."""
 import ctypes
@@ -104,10 +105,12 @@ def make_decoder(c, param_grad):
     return dec
 
 
-def decode_and_backward(dec, c, code):
+def decode_and_backward(dec, c, code, between=None):
     cut = [(int(c.offsets[s]), int(c.offsets[s + 1])) for s in range(c.S)]
     sig, rgb, num = dec.point_decode([cu(c.xyz[a:b]) for a, b in cut], [cu(c.dirs[a:b]) for a, b in cut], code)
     assert num == list(c.sizes)
+    if between is not None:
+        between()
     if sig.requires_grad:
         torch.autograd.backward((sig, rgb), (cu(c.g_sigma), cu(c.g_rgb)))
     return cut
@@ -126,9 +129,21 @@ def calls(monkeypatch):
     return n
 
 
+def check_code_gradient(name, c, cut, got):
+    """``got`` (S,3,6,H,W) numpy under the end-to-end bounds of the code gradient around the float64 reference of the family's own weights"""
+    from ssdnerf_amd import _cabi as C
+    _, gf, B, _ = G.sample_reference(name, False, False)
+    lay = (ctypes.c_uint64 * 6)()
+    C.lib().ssdnerf_point_decode_backward_layout(C.u32(c.S), C.u32(len(c.xyz)), C.u32(c.H), C.u32(c.W), lay)
+    K = int(lay[5])                                                          # the split count of the code gradient's reduction
+    for s, (a, b) in enumerate(cut):
+        e_ref, e_bnd = G.scatter_e2e_ref(c.xyz[a:b], gf[a:b], B[a:b], c.H, c.W, K)
+        bad, worst = G.check_le(got[s], e_ref, e_bnd)
+        assert bad == 0, (name, s, bad, worst)
+
+
 @pytest.mark.parametrize("name", MULTI_SCENE)
 def test_point_decode_leaves_the_reference_gradients_in_parameters_and_code(name, calls):
-    from ssdnerf_amd import _cabi as C
     c, r = G.sample_case(name), PG.reference(name)
     dec = make_decoder(c, "fused")
     code = cu(c.code).requires_grad_(True)
@@ -141,16 +156,8 @@ def test_point_decode_leaves_the_reference_gradients_in_parameters_and_code(name
         assert got is not None and got.dtype == torch.float32 and tuple(got.shape) == ref[k].shape, k
         bad, worst = PG.check_le(got.cpu().numpy(), np.ascontiguousarray(ref[k]), np.ascontiguousarray(bnd[k]))
         assert bad == 0, (name, k, bad, worst)
-    # the code's gradient: the unchanged launches of ssdnerf_point_decode_backward, under that gradient's own end-to-end bounds
-    _, gf, B, _ = G.sample_reference(name, False, False)
-    lay = (ctypes.c_uint64 * 6)()
-    C.lib().ssdnerf_point_decode_backward_layout(C.u32(c.S), C.u32(len(c.xyz)), C.u32(c.H), C.u32(c.W), lay)
-    K = int(lay[5])                                                          # the split count of the code gradient's reduction
-    got = code.grad.cpu().numpy()
-    for s, (a, b) in enumerate(cut):
-        e_ref, e_bnd = G.scatter_e2e_ref(c.xyz[a:b], gf[a:b], B[a:b], c.H, c.W, K)
-        bad, worst = G.check_le(got[s], e_ref, e_bnd)
-        assert bad == 0, (name, s, bad, worst)
+    # the code's gradient: the launches of ssdnerf_point_decode_backward, under that gradient's own end-to-end bounds
+    check_code_gradient(name, c, cut, code.grad.cpu().numpy())
 
 
 def test_a_frozen_parameter_gets_no_gradient_and_a_frozen_code_none(calls):
@@ -171,6 +178,22 @@ def test_a_frozen_parameter_gets_no_gradient_and_a_frozen_code_none(calls):
             assert PG.check_le(params[k].grad.cpu().numpy(), np.ascontiguousarray(ref[k]), np.ascontiguousarray(bnd[k]))[0] == 0, k
 
 
+def test_a_frozen_decoder_gets_the_gradient_of_the_weights_its_forward_read(calls):
+    """the backward reads the packed block the forward read: a weight doubled in place between the two does not reach the code's gradient, which stays under the
+    end-to-end bounds around the reference of the ORIGINAL weights (re-packing at backward time would differentiate the doubled network)"""
+    name = "ragged-fp32-aligned"
+    c = G.sample_case(name)
+    dec = make_decoder(c, "eager").requires_grad_(False)
+    code = cu(c.code).requires_grad_(True)
+
+    def double():
+        with torch.no_grad():
+            dec.base_net[0].weight.mul_(2)
+    cut = decode_and_backward(dec, c, code, between=double)
+    assert calls == [] and not np.array_equal(dec.packed_params().cpu().numpy(), c.P)        # (the change is real: the next forward packs the doubled weights)
+    check_code_gradient(name, c, cut, code.grad.cpu().numpy())
+
+
 def test_without_gradients_and_in_eager_mode_the_call_sequence_is_the_present_one(calls, monkeypatch):
     c = G.sample_case("ragged-fp32-aligned")
     dec = make_decoder(c, "fused")
@@ -180,7 +203,7 @@ def test_without_gradients_and_in_eager_mode_the_call_sequence_is_the_present_on
     with torch.no_grad():                                                    # no gradient: the fused forward alone
         decode_and_backward(dec, c, cu(c.code).requires_grad_(True))
     assert calls == [] and entered == []
-    dec.requires_grad_(False)                                                # a frozen decoder: ``_PointDecodeFn``, as before
+    dec.requires_grad_(False)                                                # a frozen decoder: the code-gradient launches alone, as before
     code = cu(c.code).requires_grad_(True)
     decode_and_backward(dec, c, code)
     assert calls == [] and entered == [] and code.grad is not None

@@ -1,12 +1,13 @@
 """The decode of the joint iteration of a training step with a TRAINABLE decoder: ``param_grad='eager'`` (grid_sample + nn.Linear under autograd, the default) against
-``param_grad='fused'`` (the fused decode forward, ``ssdnerf_point_decode_backward_params`` and the unchanged code-gradient launches; csrc/decode_bwd_params.hip).
+``param_grad='fused'`` (the fused decode forward, ``ssdnerf_point_decode_backward_params`` and the code-gradient launches: one ``_PointDecodeFn``; csrc/decode_bwd_params.hip).
 
 At the joint step's shape -- 8 scenes x 2^12 rays, the synthetic object scenes of the stage-1 model of tests/test_tv_loss_gpu.py, the samples the train march yields
 (captured from a real ``train_step``) -- it reports, by HIP events, median (min - max) over windows taken in turn:
   * ``param_launches_ms``   the two new launches alone, through the C ABI;
-  * ``code_launches_ms``    the three launches of ``ssdnerf_point_decode_backward`` next to them (unchanged);
+  * ``code_launches_ms``    the three launches of ``ssdnerf_point_decode_backward`` next to them;
   * ``fused_fwd_bwd_ms``    ``point_decode`` + backward with ``param_grad='fused'``: everything the mode runs, Python included;
   * ``eager_fwd_bwd_ms``    the same with ``param_grad='eager'``: what it replaces;
+  * ``frozen_fwd_bwd_ms``   the same call on a frozen copy of the decoder, gradient w.r.t. the code only: the path of guidance and fine-tuning;
   * ``train_step``          ms per ``MultiSceneNeRF.train_step`` (``extra_scene_step=15``, ``HIPAdam``) in both modes, host clock over synchronised windows, with
                             ``gap_exceeds_spread``: whether the two modes' [min, max] intervals are disjoint.
 The upstream gradients of the isolated timings are random and non-zero on every sample (no sample is skipped: the launches' worst case).  The speed is reported, not
@@ -14,6 +15,7 @@ promised; the default path is the parent commit's.
 
 Prints one JSON line.   usage: python tools/bench_decode_param_grad.py [--iters 20] [--windows 5] [--calls 3] > profiles/decode_param_grad.json"""
 import argparse
+import copy
 import ctypes
 import json
 import os
@@ -137,8 +139,13 @@ def main():
             sig, rgb, _ = dec.point_decode(xyzs, dirs, leaf)
             torch.autograd.grad((sig, rgb), [leaf] + params, (gs, gc))
         return run
-    iso = _alternate({"param_launches_ms": param_launches, "code_launches_ms": code_launches, "fused_fwd_bwd_ms": fwd_bwd("fused"), "eager_fwd_bwd_ms": fwd_bwd("eager")},
-                     args.iters, args.windows, warmup=3)
+    frozen = copy.deepcopy(dec).requires_grad_(False)
+
+    def frozen_fwd_bwd():
+        sig, rgb, _ = frozen.point_decode(xyzs, dirs, leaf)
+        torch.autograd.grad((sig, rgb), [leaf], (gs, gc))
+    iso = _alternate({"param_launches_ms": param_launches, "code_launches_ms": code_launches, "fused_fwd_bwd_ms": fwd_bwd("fused"), "eager_fwd_bwd_ms": fwd_bwd("eager"),
+                      "frozen_fwd_bwd_ms": frozen_fwd_bwd}, args.iters, args.windows, warmup=3)
     dec.param_grad = "fused"
     res = dict(tool="bench_decode_param_grad", device=torch.cuda.get_device_name(0), scenes=SCENES, rays_per_scene=RAYS, samples_total=total,
                samples_per_scene=num, planes=[int(hp), int(wp)], plane_dtype=str(dec.plane_dtype).replace("torch.", ""),
